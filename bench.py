@@ -11,7 +11,13 @@ kernel [+ library-wide kernels for the rare queries that need them]); with N > 1
 (one process per GPU, torchrun) each rank scores its own 65,536 queries (weak scaling) and
 the step also gathers the compacted top-k records on rank 0 over RCCL.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (the headline figure,
+`ms_per_step` and the configuration). `--dump-outputs DIR` also writes what the last timed step
+returned as DIR/<name>.npy (dump_outputs). `--full` adds everything that takes runs of its own: the
+batch statistics and the roofline built on them (one more untimed step), the drop-in scoreBatch /
+score() legs and the CPU baseline.
 """
 from __future__ import annotations
 
@@ -369,6 +375,42 @@ class StepLoop:
         return elapsed, self.ktimes
 
 
+DUMP_ROWS = 16384  # queries whose records are dumped: 16384 x 100 x (8 + 4) B = 20 MB at limit 100
+DUMP_SEED = 20261019
+
+
+def dump_outputs(path: str, loop: StepLoop) -> None:
+    """Writes what the last timed step handed its caller (the counts / keys / scores buffers
+    ngsSearchDevice filled for this rank's batch) as .npy files under `path`:
+
+      counts.npy  float64 [B]               results of every query of the batch
+      rows.npy    float64 [R]               the queries whose records follow: all B if B <= 16,384,
+                                            otherwise a fixed seeded sample of 16,384, ascending
+      keys.npy    float64 [R, stride]       key ids of those queries' results, best first
+      scores.npy  float32 [R, stride]       their scores
+
+    Slots past a query's count are not part of the answer (the library leaves them as they were)
+    and are written as -1 (keys) and 0 (scores)."""
+    import numpy as np
+    gb = loop.gbs[(loop.nstep - 1) % loop.nbuf]  # the buffer the last step wrote (StepLoop.step)
+    B, stride = loop.B, loop.stride
+    counts = gb.counts.cpu().numpy().astype(np.int64)
+    if B <= DUMP_ROWS:
+        rows = np.arange(B)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, DUMP_ROWS, replace=False))
+    sel = torch.from_numpy(rows).to(gb.keys.device)
+    keys = gb.keys[:B * stride].view(B, stride)[sel].cpu().numpy().astype(np.float64)
+    scores = gb.scores[:B * stride].view(B, stride)[sel].cpu().numpy().astype(np.float32)
+    unused = np.arange(stride)[None, :] >= counts[rows][:, None]
+    keys[unused] = -1.0
+    scores[unused] = 0.0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("counts", counts.astype(np.float64)), ("rows", rows.astype(np.float64)),
+                    ("keys", keys), ("scores", scores)):
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def serialised_roofline(pmc, st, version):
     """The dominant kernel alone: the main k_wave_lean launch's own algorithmic bytes (4 B per posting
     and 16 B per list opened, of the queries it finished: this run's ngsLastStats) over its mean
@@ -401,7 +443,69 @@ def pmc_record(cfg_name: str):
     return d
 
 
-def main():
+def full_legs(out, args, cfg, corpus, L, h, loop, ktimes, raw, offs, elapsed, rank, world, local):
+    """--full: what takes runs of its own, added to the result line `out`: the batch statistics and
+    the roofline built on them, the drop-in scoreBatch / score() legs and the CPU baseline."""
+    B, depth, stride = loop.B, loop.depth, loop.stride
+    if depth > 1:
+        # the batch's statistics (postings, lists, paths: the algorithmic bytes) come with the
+        # per-call timing, off in the timed steps: one more batch, untimed, with it on
+        L.ngsSetTiming(h, 1)
+        loop.depth = 1
+        loop.step()
+        loop.drain()
+        L.ngsSetTiming(h, 0)
+    st = loop.st
+
+    # per-launch algorithmic bytes of the fused kernel (DESIGN.md §Roofline)
+    qbytes = offs[-1] * (4 if corpus.wide else 1)
+    alg_bytes = (4 * st.postings + 16 * st.lists + qbytes + 16 * st.survivors + 8 * st.results + 4 * B)
+    fast_ms = sum(k[0] for k in ktimes) / len(ktimes)  # per-batch tier-1 phase (HIP events)
+    step_ms = elapsed / args.steps * 1e3
+    # with batches pipelined the per-batch phases overlap: the roofline is taken over the whole
+    # step instead (every kernel of a batch, per GPU), the conservative figure
+    roof_ms = fast_ms if depth == 1 else step_ms
+    achieved = alg_bytes / (roof_ms * 1e-3) / 1e9
+    pmc = pmc_record(args.config)
+    version = out["detail"]["library"]
+    out["roofline"] = {
+        "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 4),
+        "traffic": pmc.get("hbm_bytes_per_launch") if pmc else None,
+        "traffic_source": ({"file": pmc["file"], "fetch_pass": pmc.get("source"),
+                            "profiled_library": pmc.get("library"), "this_library": version,
+                            "same_source": pmc.get("library") == version} if pmc else None),
+        "kernel": ("tier-1 phase: k_wave_lean over the batch + k_emit, beside it k_wave_lean + k_emit on the "
+                   "heavy list and k_wave on the full list (side streams), hand-over k_wave, k_fast (HIP "
+                   "events on the call stream)" if depth == 1 else
+                   f"whole step: every kernel of one batch (k_prep, the tier-1 phase, k_fast), batches "
+                   f"pipelined {depth} deep (ngsSearchDeviceAsync); per-GPU step time"),
+        "kernel_ms": round(roof_ms, 4), "alg_bytes_per_launch": alg_bytes,
+        "postings_per_query": round(st.postings / max(1, st.fast_queries), 1),
+        "serialised": serialised_roofline(pmc, st, version)}
+    out["detail"].update({
+        "phase_ms": round(fast_ms, 4) if depth == 1 else None,
+        "prep_ms": round(sum(k[1] for k in ktimes) / len(ktimes), 4) if depth == 1 else None,
+        "general_ms": round(sum(k[2] for k in ktimes) / len(ktimes), 4) if depth == 1 else None,
+        "general_queries": int(st.general_queries), "results_per_query": round(st.results / B, 2),
+        "survivors_per_query": round(st.survivors / B, 2),
+        "paths": {"tier1a_finished": int(st.fast_queries), "heavy_listed": int(st.heavy_queries),
+                  "full_listed": int(st.full_queries), "tier1b_handovers": int(st.handover_queries),
+                  "tier2": int(st.tier2_queries), "general": int(st.general_queries),
+                  "slot_full": int(st.slot_full_queries)},
+        "survivor_slots": int(st.survivor_slots)})
+    if rank == 0 and world == 1 and not args.no_dropin and not corpus.wide:
+        out["detail"]["dropin"] = dropin_path(L, h, cfg, raw, offs)
+        out["detail"]["dropin"].update(c1_latency(local))
+        out["detail"]["dropin"]["note"] = ("scoreBatch: host strings in, new[]'d char**/float* out (released), "
+                                           "PCIe both ways, whole batch; score(): one query per call")
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(corpus, cfg, raw, offs)
+        if args.config in REFERENCE_DLL:  # the reference itself, measured where it compiles (BASELINE.md)
+            out["cpu_baseline"]["reference_dll"] = REFERENCE_DLL[args.config]
+
+
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
@@ -409,12 +513,18 @@ def main():
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--rows", type=int, default=None, help="override corpus rows (debug only)")
     ap.add_argument("--batch", type=int, default=None, help="override per-GPU batch (debug only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the scoreBatch / score() latency lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: batch statistics and roofline (one more "
+                         "untimed step), the drop-in scoreBatch / score() legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-dropin", action="store_true",
+                    help="with --full: skip the scoreBatch / score() latency lines")
     ap.add_argument("--depth", type=int, default=None,
                     help="batches in flight (ngsSearchDeviceAsync; default 2, C2 3); 1 = one blocking "
                          "ngsSearchDevice per step")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     cfg = dict(CONFIGS[args.config])
     if args.rows:
         cfg["rows"] = args.rows
@@ -452,69 +562,31 @@ def main():
         d_off = torch.tensor(offs, dtype=torch.int64, device=dev)
     stride = min(cfg["limit"], n_keys)
     depth = max(1, args.depth if args.depth is not None else cfg.get("depth", 2))
-    # HIP-event kernel timing per call (four event records) only where the roofline uses it (depth 1):
-    # with batches in flight the step time is the denominator, and a C2 step is ~20 host calls
-    L.ngsSetTiming(h, 1 if depth == 1 else 0)
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    # HIP-event kernel timing per call (four event records) only where the roofline uses it (--full at
+    # depth 1): with batches in flight the step time is the denominator, and a C2 step is ~20 host calls
+    L.ngsSetTiming(h, 1 if depth == 1 and args.full else 0)
     loop = StepLoop(L, h, d_raw, d_off, B, cfg["threshold"], cfg["limit"], stride, depth, world, dev,
                     torch.cuda.current_stream(dev).cuda_stream)
     warmup = args.warmup if args.warmup is not None else cfg.get("warmup", 10)
     elapsed, ktimes = loop.run(args.steps, warmup)
-    if depth > 1:
-        # the batch's statistics (postings, lists, paths: the algorithmic bytes) come with the
-        # per-call timing, off in the timed steps: one more batch, untimed, with it on
-        L.ngsSetTiming(h, 1)
-        loop.depth = 1
-        loop.step()
-        loop.drain()
-        L.ngsSetTiming(h, 0)
-    st = loop.st
-
-    # per-launch algorithmic bytes of the fused kernel
-    qbytes = offs[-1] * (4 if corpus.wide else 1)
-    alg_bytes = (4 * st.postings + 16 * st.lists + qbytes + 16 * st.survivors + 8 * st.results + 4 * B)
-    fast_ms = sum(k[0] for k in ktimes) / len(ktimes)  # per-batch tier-1 phase (HIP events)
-    step_ms = elapsed / args.steps * 1e3
-    # with batches pipelined the per-batch phases overlap: the roofline is taken over the whole
-    # step instead (every kernel of a batch, per GPU), the conservative figure
-    roof_ms = fast_ms if depth == 1 else step_ms
-    achieved = alg_bytes / (roof_ms * 1e-3) / 1e9
-    pmc = pmc_record(args.config)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop)
     version = L.ngsVersion().decode()
     total_q = B * world * args.steps
     value = total_q / elapsed / 1e6
     out = {
         "metric": METRIC, "value": round(value, 4), "unit": "Mqueries/s", "n_gpus": world, "steps": args.steps,
         "warmup": warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+        "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic", "full": args.full,
         "config": {"workload": cfg["workload"], "rows": cfg["rows"], "batch_per_gpu": B,
                    "threshold": cfg["threshold"], "limit": cfg["limit"], "weights": cfg["weights"],
                    "parallelism": f"query-shard x{world}" + (" + RCCL gather of top-k" if world > 1 else "")},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "traffic": pmc.get("hbm_bytes_per_launch") if pmc else None,
-                     "traffic_source": ({"file": pmc["file"], "fetch_pass": pmc.get("source"),
-                                         "profiled_library": pmc.get("library"), "this_library": version,
-                                         "same_source": pmc.get("library") == version} if pmc else None),
-                     "kernel": ("tier-1 phase: k_wave_lean over the batch + k_emit, beside it k_wave_lean + k_emit on the "
-                                "heavy list and k_wave on the full list (side streams), hand-over k_wave, k_fast (HIP "
-                                "events on the call stream)" if depth == 1 else
-                                f"whole step: every kernel of one batch (k_prep, the tier-1 phase, k_fast), batches "
-                                f"pipelined {depth} deep (ngsSearchDeviceAsync); per-GPU step time"),
-                     "kernel_ms": round(roof_ms, 4), "alg_bytes_per_launch": alg_bytes,
-                     "postings_per_query": round(st.postings / max(1, st.fast_queries), 1),
-                     "serialised": serialised_roofline(pmc, st, version)},
-        "detail": {"phase_ms": round(fast_ms, 4) if depth == 1 else None, "depth": depth,
-                   "prep_ms": round(sum(k[1] for k in ktimes) / len(ktimes), 4) if depth == 1 else None,
-                   "general_ms": round(sum(k[2] for k in ktimes) / len(ktimes), 4) if depth == 1 else None,
-                   "general_queries": int(st.general_queries), "results_per_query": round(st.results / B, 2),
-                   "survivors_per_query": round(st.survivors / B, 2), "index_build_s": round(index_s, 2),
-                   "corpus_gen_s": round(corpus_s, 2),
-                   "paths": {"tier1a_finished": int(st.fast_queries), "heavy_listed": int(st.heavy_queries),
-                             "full_listed": int(st.full_queries), "tier1b_handovers": int(st.handover_queries),
-                             "tier2": int(st.tier2_queries), "general": int(st.general_queries),
-                             "slot_full": int(st.slot_full_queries)},
-                   "survivor_slots": int(st.survivor_slots),
-                   "library": L.ngsVersion().decode()},
+        "roofline": None,  # (--full)
+        "detail": {"depth": depth, "index_build_s": round(index_s, 2), "corpus_gen_s": round(corpus_s, 2),
+                   "library": version},
+        "cpu_baseline": None,  # (--full)
     }
     if world > 1 and loop.gather_words:  # the packed gather's bytes per rank and step
         out["detail"]["gather"] = {
@@ -523,17 +595,8 @@ def main():
             "regathers": int(loop.cap.regathers), "cap_records": int(loop.cap.total),
             "note": "packed [batch, total, counts, {key, score} records] up to a record capacity every rank "
                     "holds; an overflowing batch is gathered again whole when its gather is retired"}
-    if rank == 0 and world == 1 and not args.no_dropin and not corpus.wide:
-        out["detail"]["dropin"] = dropin_path(L, h, cfg, raw, offs)
-        out["detail"]["dropin"].update(c1_latency(local))
-        out["detail"]["dropin"]["note"] = ("scoreBatch: host strings in, new[]'d char**/float* out (released), "
-                                           "PCIe both ways, whole batch; score(): one query per call")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(corpus, cfg, raw, offs)
-        if args.config in REFERENCE_DLL:  # the reference itself, measured where it compiles
-            out["cpu_baseline"]["reference_dll"] = REFERENCE_DLL[args.config]
-    else:
-        out["cpu_baseline"] = None
+    if args.full:
+        full_legs(out, args, cfg, corpus, L, h, loop, ktimes, raw, offs, elapsed, rank, world, local)
     if rank == 0:
         print(json.dumps(out), flush=True)
     L.dispose(h)

@@ -1,8 +1,10 @@
 """The CPU restatement against the REFERENCE itself on random corpora with large weights (CPU).
 
-The reference (nGramSearch/dllmain.cpp, compiled from /root/reference by oracle/Makefile into
-oracle/_ref/, this container only) and oracle/ngs_oracle.c answer the same seeded cases; the
-answers are compared tie-aware (tests/tiecheck.py). Weights come from {1, 100, 150, 1000, 0, -1}
+The reference (nGramSearch/dllmain.cpp) and oracle/ngs_oracle.c answer the same seeded cases; the
+answers are compared tie-aware (tests/tiecheck.py). The reference's answers to every case are
+recorded under tests/golden/fuzz/ (tests/golden/make_golden_fuzz.py writes them), so the fuzz runs
+wherever the suite does; where oracle/Makefile has compiled the reference into oracle/_ref/, the
+same cases are also put to the compiled reference itself. Weights come from {1, 100, 150, 1000, 0, -1}
 (plus 0.5 and 2), so scores w*s above, at and below the promotion score 100 meet promoted keys
 (nGramSearch.hpp:326-337): a promoted key is the score 100 in ScoreComparer
 (nGramSearch.h:262-269), so a key with w*s = 150 ranks above it and one at exactly 100 ties
@@ -17,44 +19,98 @@ whose multi-pair keys take "the last pair in hash order" (hpp:356-369), are not 
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 import random
-import subprocess
-
-import pytest
 
 from oracle_py import OracleIndex
-from tiecheck import bits, check
+from tiecheck import bits, check, f32
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_SRC = "/root/reference/nGramSearch/dllmain.cpp"
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libStringSearchLib.so")
+RECORDED = os.path.join(ROOT, "tests", "golden", "fuzz")
 WEIGHTS = [1.0, 100.0, 150.0, 1000.0, 0.0, -1.0, 0.5, 2.0]
 
 
-def _ref():
-    if not os.path.exists(REF_SO):
-        if not os.path.exists(REF_SRC):
-            pytest.skip("reference sources absent (GPU box): the fuzz runs in the build container")
-        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True)
-    L = C.CDLL(REF_SO)
-    L.indexN.restype = C.c_uint32
-    L.indexN.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_uint16, C.POINTER(C.c_float)]
-    L.score.restype = C.c_uint32
-    L.score.argtypes = [C.c_uint32, C.c_char_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
-                        C.c_float, C.c_uint32]
-    L.release.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_float)]
-    L.dispose.argtypes = [C.c_uint32]
-    return L
+class LiveReference:
+    """The compiled reference (oracle/_ref/libStringSearchLib.so) through its C ABI."""
+
+    def __init__(self):
+        L = C.CDLL(REF_SO)
+        L.indexN.restype = C.c_uint32
+        L.indexN.argtypes = [C.POINTER(C.c_char_p), C.c_uint64, C.c_uint16, C.POINTER(C.c_float)]
+        L.score.restype = C.c_uint32
+        L.score.argtypes = [C.c_uint32, C.c_char_p, C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.POINTER(C.c_float)),
+                            C.c_float, C.c_uint32]
+        L.release.argtypes = [C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_float)]
+        L.dispose.argtypes = [C.c_uint32]
+        self.L, self.h = L, 0
+
+    def open(self, words, row, weights):
+        wa = (C.c_char_p * len(words))(*words)
+        wf = (C.c_float * len(weights))(*weights)
+        self.h = self.L.indexN(wa, len(words), row, wf)
+        assert self.h
+
+    def score(self, q: bytes, thr: float, limit: int):
+        res = C.POINTER(C.c_char_p)()
+        sc = C.POINTER(C.c_float)()
+        n = self.L.score(self.h, q, C.byref(res), C.byref(sc), thr, limit)
+        out = [(res[i], sc[i]) for i in range(n)]
+        self.L.release(self.h, res, sc)
+        return out
+
+    def full(self, q, thr, limits):
+        return self.score(q, thr, 0)
+
+    def count(self, q, thr, limit):
+        return len(self.score(q, thr, limit))
+
+    def close(self):
+        self.L.dispose(self.h)
 
 
-def ref_score(L, h, q: bytes, thr: float, limit: int):
-    res = C.POINTER(C.c_char_p)()
-    sc = C.POINTER(C.c_float)()
-    n = L.score(h, q, C.byref(res), C.byref(sc), thr, limit)
-    out = [(res[i], sc[i]) for i in range(n)]
-    L.release(h, res, sc)
-    return out
+class RecordingReference(LiveReference):
+    """The compiled reference, keeping what it answered: per query its full (limit 0) answer and
+    the number of results at every limit of the case (tests/golden/make_golden_fuzz.py)."""
+
+    def __init__(self):
+        super().__init__()
+        self.queries = []
+
+    def full(self, q, thr, limits):
+        out = self.score(q, thr, 0)
+        self.queries.append({"q": q.decode("latin-1"), "full": [[k.decode("latin-1"), bits(s)] for k, s in out],
+                             "n": [len(out) if lim == 0 else len(self.score(q, thr, lim)) for lim in limits]})
+        return out
+
+
+class RecordedReference:
+    """The reference's recorded answers (tests/golden/fuzz/<name>.json), read back in case order."""
+
+    def __init__(self, name):
+        with open(os.path.join(RECORDED, name + ".json")) as f:
+            self.queries = iter(json.load(f)["queries"])
+        self.rec = self.limits = None
+
+    def open(self, words, row, weights):
+        pass
+
+    def full(self, q, thr, limits):
+        self.rec, self.limits = next(self.queries), limits
+        assert self.rec["q"] == q.decode("latin-1"), f"recorded case stream out of step at {q!r}"
+        return [(k.encode("latin-1"), f32(b)) for k, b in self.rec["full"]]
+
+    def count(self, q, thr, limit):
+        return self.rec["n"][self.limits.index(limit)]
+
+    def close(self):
+        pass
+
+
+def references(name):
+    """The recorded answers, and the compiled reference where it was built."""
+    return [RecordedReference(name)] + ([LiveReference()] if os.path.exists(REF_SO) else [])
 
 
 def _corpus(rng: random.Random):
@@ -104,38 +160,48 @@ def _queries(rng: random.Random, words, keys, n):
     return out
 
 
-def test_oracle_vs_reference_large_weights():
-    L = _ref()
-    rng = random.Random(20261018)
+def fuzz(ref, seed, n_cases, n_queries, thresholds, limits):
+    """Puts the seeded cases to `ref` and to the oracle; (cases, order-dependent cases, failures)."""
+    rng = random.Random(seed)
     cases = ambiguous = 0
     failures = []
-    while cases < 6000:
+    while cases < n_cases:
         words, row, weights, keys = _corpus(rng)
-        wa = (C.c_char_p * len(words))(*words)
-        wf = (C.c_float * len(weights))(*weights)
-        h = L.indexN(wa, len(words), row, wf)
-        assert h
+        ref.open(words, row, weights)
         oi = OracleIndex(words, row, weights)
-        for q in _queries(rng, words, keys, 12):
-            thr = rng.choice([0.0, 0.0, 0.3, 0.5])
-            full = ref_score(L, h, q, thr, 0)
-            for limit in (1, 3, 100, 0):
+        for q in _queries(rng, words, keys, n_queries):
+            thr = rng.choice(thresholds)
+            full = ref.full(q, thr, limits)
+            for limit in limits:
                 cases += 1
                 ours, amb = oi.score_amb(q, thr, limit)
                 if amb:
                     ambiguous += 1
                     continue
-                ref = full if limit == 0 else ref_score(L, h, q, thr, limit)
+                n_ref = len(full) if limit == 0 else ref.count(q, thr, limit)
+                if limit >= 2**31:
+                    assert n_ref == len(full), (q, thr, limit)
                 try:
-                    check(ours, len(ref), [k for k, _ in full], [bits(s) for _, s in full],
+                    check(ours, n_ref, [k for k, _ in full], [bits(s) for _, s in full],
                           f"words={words} row={row} w={weights} q={q!r} thr={thr} limit={limit}")
                 except AssertionError as e:
                     failures.append(str(e))
-        L.dispose(h)
+        ref.close()
         oi.close()
-    print(f"{cases} cases, {ambiguous} order-dependent in the reference (skipped), {len(failures)} failures")
-    assert not failures, f"{len(failures)} of {cases} cases differ; first: {failures[0]}"
-    assert ambiguous < cases // 10
+    return cases, ambiguous, failures
+
+
+LARGE_WEIGHTS = dict(seed=20261018, n_cases=6000, n_queries=12, thresholds=[0.0, 0.0, 0.3, 0.5],
+                     limits=[1, 3, 100, 0])
+
+
+def test_oracle_vs_reference_large_weights():
+    for ref in references("large_weights"):
+        cases, ambiguous, failures = fuzz(ref, **LARGE_WEIGHTS)
+        print(f"{type(ref).__name__}: {cases} cases, {ambiguous} order-dependent in the reference (skipped), "
+              f"{len(failures)} failures")
+        assert not failures, f"{len(failures)} of {cases} cases differ; first: {failures[0]}"
+        assert ambiguous < cases // 10
 
 
 # thresholds outside [0, 1], NaN and near 1, limits past 2^31 (VERDICT r5 ask 3): the reference tests
@@ -144,39 +210,14 @@ def test_oracle_vs_reference_large_weights():
 # uint32 taken as given (hpp:399-401, 420-425), 0 meaning every result
 DEGENERATE_THRESHOLDS = [-1.0, float("nan"), 1.0, 1.5, 0.999, 1.0 / 3.0, 2.0 / 3.0, 0.7]
 DEGENERATE_LIMITS = [1, 2**31, 2**32 - 1, 0]
+DEGENERATE = dict(seed=61018, n_cases=2000, n_queries=8, thresholds=DEGENERATE_THRESHOLDS,
+                  limits=DEGENERATE_LIMITS)
 
 
 def test_oracle_vs_reference_degenerate_args():
-    L = _ref()
-    rng = random.Random(61018)
-    cases = ambiguous = 0
-    failures = []
-    while cases < 2000:
-        words, row, weights, keys = _corpus(rng)
-        wa = (C.c_char_p * len(words))(*words)
-        wf = (C.c_float * len(weights))(*weights)
-        h = L.indexN(wa, len(words), row, wf)
-        assert h
-        oi = OracleIndex(words, row, weights)
-        for q in _queries(rng, words, keys, 8):
-            thr = rng.choice(DEGENERATE_THRESHOLDS)
-            full = ref_score(L, h, q, thr, 0)
-            for limit in DEGENERATE_LIMITS:
-                cases += 1
-                ours, amb = oi.score_amb(q, thr, limit)
-                if amb:
-                    ambiguous += 1
-                    continue
-                ref = full if limit == 0 else ref_score(L, h, q, thr, limit)
-                if limit >= 2**31:
-                    assert len(ref) == len(full), (q, thr, limit)
-                try:
-                    check(ours, len(ref), [k for k, _ in full], [bits(s) for _, s in full],
-                          f"words={words} row={row} w={weights} q={q!r} thr={thr} limit={limit}")
-                except AssertionError as e:
-                    failures.append(str(e))
-        L.dispose(h)
-        oi.close()
-    print(f"{cases} cases, {ambiguous} order-dependent in the reference (skipped), {len(failures)} failures")
-    assert not failures, f"{len(failures)} of {cases} cases differ; first: {failures[0]}"
-    assert ambiguous < cases // 10
+    for ref in references("degenerate_args"):
+        cases, ambiguous, failures = fuzz(ref, **DEGENERATE)
+        print(f"{type(ref).__name__}: {cases} cases, {ambiguous} order-dependent in the reference (skipped), "
+              f"{len(failures)} failures")
+        assert not failures, f"{len(failures)} of {cases} cases differ; first: {failures[0]}"
+        assert ambiguous < cases // 10

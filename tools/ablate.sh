@@ -4,10 +4,12 @@
 #   1: stage + load, no counting   2: sketch adds only (no candidate pass)   4: no candidate resolution
 #   8: staging without the loads (synthetic term ids)
 # usage (GPU box, repo root): tools/ablate.sh "<flags>" [bench args...]
+# The bench lines go to $NGS_OUT/abl (default out/abl).
 set -o pipefail
 FLAGS=$1; shift
-mkdir -p gpurun_out/abl
+O=${NGS_OUT:-out}/abl
+mkdir -p $O
 for f in $FLAGS; do
-  NGS_DEBUG=$f timeout -k 10 240 python3 bench.py --no-cpu-baseline --steps 50 --warmup 3 "$@" > gpurun_out/abl/$f.json 2> gpurun_out/abl/$f.err || { echo "dbg $f failed"; tail -3 gpurun_out/abl/$f.err; exit 1; }
-  python3 -c "import json; d=json.load(open('gpurun_out/abl/$f.json')); print(f\"NGS_DEBUG=$f ${NGS_LIB:-main}: tier1 {d['roofline']['kernel_ms']:.3f} ms\")"
+  NGS_DEBUG=$f timeout -k 10 240 python3 bench.py --full --no-cpu-baseline --steps 50 --warmup 3 "$@" > $O/$f.json 2> $O/$f.err || { echo "dbg $f failed"; tail -3 $O/$f.err; exit 1; }
+  python3 -c "import json; d=json.load(open('$O/$f.json')); print(f\"NGS_DEBUG=$f ${NGS_LIB:-main}: tier1 {d['roofline']['kernel_ms']:.3f} ms\")"
 done

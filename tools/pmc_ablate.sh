@@ -9,7 +9,7 @@ FLAGS=$1; shift
 OUT=gpurun_out/pmc_abl
 mkdir -p $OUT
 for f in $FLAGS; do
-  NGS_DEBUG=$f timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_INSTS_BRANCH -d $OUT/d$f -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-dropin --steps 3 --warmup 1 "$@" > $OUT/d$f.log 2>&1 || { echo "dbg $f failed"; tail -5 $OUT/d$f.log; exit 1; }
+  NGS_DEBUG=$f timeout -s KILL 120 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_INSTS_BRANCH -d $OUT/d$f -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-dropin --steps 3 --warmup 1 "$@" > $OUT/d$f.log 2>&1 || { echo "dbg $f failed"; tail -5 $OUT/d$f.log; exit 1; }
   python3 - "$OUT/d$f" "$f" <<'P'
 import csv, glob, sys, collections
 root, flag = sys.argv[1], sys.argv[2]

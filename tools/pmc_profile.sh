@@ -17,7 +17,7 @@ PASSES=(
 )
 i=0
 for p in "${PASSES[@]}"; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $p -d "$OUT/p$i" -o run --output-format csv -- python3 bench.py --no-cpu-baseline "$@" > "$OUT/p$i.log" 2>&1 || { echo "pass $i failed"; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $p -d "$OUT/p$i" -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline "$@" > "$OUT/p$i.log" 2>&1 || { echo "pass $i failed"; exit 1; }
   echo "pass $i done: $p"
   i=$((i+1))
 done
