@@ -116,6 +116,40 @@ NGS_API uint64_t getSizeW(uint32_t handle);
 NGS_API uint64_t getLibSizeW(uint32_t handle);
 
 /* ------------------------------------------------------------------------------------
+ * UTF-8 on wide indexes. Linux hosts hold UTF-8 (files, databases, Arrow and torch byte
+ * buffers, char*), not wchar_t: these entry points take and return UTF-8 and run the wide
+ * index and search underneath. They are valid on any wide handle (indexW, indexU8, or a wide
+ * index loaded from a file); on a narrow handle they answer like the width mismatch above
+ * (0 / NULL / -3). The W calls and the device entry points work on an indexU8 handle too.
+ * Decoding rule: where a well-formed UTF-8 sequence (the Unicode standard's table: no overlong
+ * forms, no surrogates, at most U+10FFFF) starts and lies inside the string, it is one character,
+ * its scalar value; any other byte b is one unit 0x110000 + b, which is not a code point and is
+ * normalised to a space like an invalid byte of the narrow API. (Python: bytes.decode('utf-8',
+ * 'surrogateescape') with U+DC80+x read as 0x110000 + 0x80 + x.) Encoding inverts it exactly, so
+ * result strings are the bytes that were indexed.
+ * ------------------------------------------------------------------------------------ */
+
+/* indexW over UTF-8 words (decoded on the host): gSize 1..3, 0 otherwise; size < 2 or
+ * words == NULL yields an un-built wide handle, as indexW. */
+NGS_API uint32_t indexU8(char** words, uint64_t size, uint16_t rowSize, float* weight, uint16_t gSize);
+/* search / score / searchBatch / scoreBatch with UTF-8 queries: the answers (keys, order, fp32
+ * scores, counts) are those of the W call on the decoded queries. Result strings are index-owned
+ * NUL-terminated UTF-8 keys (valid until dispose; the table of them is built by the first U8 call
+ * on the handle); free the arrays with release(). Batches of more than 16 queries are uploaded as
+ * UTF-8 and decoded on the GPU. On a handle with several replicas a U8 batch is answered by the
+ * first replica, not split (the results are identical). */
+NGS_API uint32_t searchU8(uint32_t handle, const char* query, char*** results, float threshold, uint32_t limit);
+NGS_API uint32_t scoreU8(uint32_t handle, const char* query, char*** results, float** scores, float threshold,
+                         uint32_t limit);
+NGS_API uint32_t scoreBatchU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                              uint32_t limit, uint32_t* counts, char*** results, float** scores);
+NGS_API uint32_t searchBatchU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                               uint32_t limit, uint32_t* counts, char*** results);
+/* UTF-8 form of ngsKeyW (NULL if out of range, un-built, or a narrow index). A key character an
+ * indexW caller stored that is neither a scalar value nor 0x110000 + b reads as U+FFFD. */
+NGS_API const char* ngsKeyU8(uint32_t handle, uint32_t keyId);
+
+/* ------------------------------------------------------------------------------------
  * Device-level extensions: inputs and outputs stay in HBM (bench, multi-GPU sharding,
  * host frameworks that already hold device buffers). Not in the reference.
  * ------------------------------------------------------------------------------------ */
@@ -171,6 +205,23 @@ NGS_API int ngsSearchDeviceAsync(uint32_t handle, const uint8_t* dQueryBytes, co
                                  uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream,
                                  uint64_t* ticket);
 NGS_API int ngsSearchDeviceWait(uint32_t handle, uint64_t ticket);
+
+/* Decodes a batch of UTF-8 strings held on the current device into the UTF-32 batch that
+ * ngsSearchDevice / ngsSearchDeviceAsync take for a wide index: string i is the bytes
+ * dBytes[dOffsets[i] .. dOffsets[i+1]) (absolute offsets, any alignment, dOffsets[0] need not be
+ * 0); its characters go to dOut (4-byte aligned) from byte dOutOffsets[i], and dOutOffsets[0..n]
+ * ascend from 0 in multiples of 4. A string whose characters would end past outCapBytes is decoded
+ * as empty, like every string after it, and nothing of it is written; outCapBytes = 4 x the input
+ * byte count always suffices. Stream-ordered on `stream` with no host wait and no handle: queued
+ * before ngsSearchDevice / ngsSearchDeviceAsync on the same stream, it gives a caller with UTF-8
+ * in HBM the whole asynchronous path. Returns 0, -3 (bad argument), -4 (HIP error). */
+NGS_API int ngsUtf8Decode(const uint8_t* dBytes, const uint64_t* dOffsets, uint32_t n, uint8_t* dOut,
+                          uint64_t outCapBytes, uint64_t* dOutOffsets, void* stream);
+/* ngsSearchDevice with UTF-8 queries on a wide handle (-3 on a narrow one): the synchronous
+ * convenience form, decoding into the call's own scratch first. Return codes as ngsSearchDevice. */
+NGS_API int ngsSearchDeviceU8(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                              uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
+                              uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream);
 
 /* Low-latency score()/search() (narrow indexes): a persistent one-wave server kernel answers
  * single queries from a request block in pinned host memory, with no kernel launch, copy or

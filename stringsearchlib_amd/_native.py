@@ -113,6 +113,26 @@ def lib():
     L.getLibSizeW.argtypes = [u32]
     L.ngsKeyW.restype = C.c_void_p
     L.ngsKeyW.argtypes = [u32, u32]
+    # UTF-8 on wide indexes: strings in and out are char*, the index underneath is the wide one
+    if hasattr(L, "indexU8"):  # (experiment builds of older sources lack them)
+        L.indexU8.restype = u32
+        L.indexU8.argtypes = [C.POINTER(cp), u64, C.c_uint16, C.POINTER(f32), C.c_uint16]
+        L.searchU8.restype = u32
+        L.searchU8.argtypes = [u32, cp, C.POINTER(PP), f32, u32]
+        L.scoreU8.restype = u32
+        L.scoreU8.argtypes = [u32, cp, C.POINTER(PP), C.POINTER(C.POINTER(f32)), f32, u32]
+        L.scoreBatchU8.restype = u32
+        L.scoreBatchU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, C.POINTER(u32), C.POINTER(PP),
+                                   C.POINTER(C.POINTER(f32))]
+        L.searchBatchU8.restype = u32
+        L.searchBatchU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, C.POINTER(u32), C.POINTER(PP)]
+        L.ngsKeyU8.restype = C.c_void_p
+        L.ngsKeyU8.argtypes = [u32, u32]
+        L.ngsUtf8Decode.restype = C.c_int
+        L.ngsUtf8Decode.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u64, C.c_void_p, C.c_void_p]
+        L.ngsSearchDeviceU8.restype = C.c_int
+        L.ngsSearchDeviceU8.argtypes = [u32, C.c_void_p, C.c_void_p, u32, f32, u32, u32, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
     L.ngsCharSize.restype = u32
     L.ngsCharSize.argtypes = [u32]
     L.ngsGramSize.restype = u32

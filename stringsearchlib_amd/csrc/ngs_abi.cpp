@@ -28,6 +28,7 @@
 #include "ngs_build.h"
 #include "ngs_index.h"
 #include "ngs_kernels.h"
+#include "ngs_utf8.h"
 
 namespace ngs {
 namespace {
@@ -359,6 +360,12 @@ struct Context {
     size_t ptemp_bytes = 0;
     GeneralBuffers gen;
     Pinned h_off, h_raw, h_res;  // queries in; results out
+    // the U8 entry points: a batch's UTF-8 bytes and byte offsets as copied in, and the decoder's
+    // scratch; the decoder writes the UTF-32 batch into d_raw / d_off (ensure_u8)
+    uint8_t* d_u8 = nullptr;
+    uint64_t* d_u8off = nullptr;
+    void* d_u8temp = nullptr;
+    size_t u8cap = 0, u8ncap = 0, u8temp_bytes = 0;
     uint8_t* d_sio = nullptr;     // the latency path's block (kSioBytes): one copy in, one copy out
     uint8_t* h_sio = nullptr;     // ... its pinned host image
     // one-stream calls (queue_search): calls built as graphs, replayed when a call's launch
@@ -375,7 +382,7 @@ struct Context {
         for (void* p : {(void*)d_raw, (void*)d_off, (void*)d_norm, (void*)d_qm, (void*)d_glist, (void*)d_list2, (void*)d_fb, (void*)d_fb2, (void*)d_heavy, (void*)d_full, (void*)d_lslots,
                         (void*)d_esn, (void*)d_est, (void*)d_esc, (void*)d_prec, (void*)d_pcnt,
                         (void*)d_eovf, (void*)d_anext, (void*)d_at, (void*)d_ac,
-                        (void*)d_group, (void*)d_stats, (void*)d_sio, (void*)d_out, (void*)d_pos, (void*)d_pk, (void*)d_ps, d_ptemp, (void*)gen.cnt,
+                        (void*)d_group, (void*)d_stats, (void*)d_sio, (void*)d_out, (void*)d_pos, (void*)d_pk, (void*)d_ps, d_ptemp, (void*)d_u8, (void*)d_u8off, d_u8temp, (void*)gen.cnt,
                         (void*)gen.kenc, (void*)gen.list, (void*)gen.sorted, (void*)gen.lcount, gen.temp})
             if (p) hipFree(p);
         for (auto& g : graphs) hipGraphExecDestroy(g.second);
@@ -600,6 +607,19 @@ struct Library {
     };
     std::mutex pend_mu;
     std::unordered_map<uint64_t, Pending> pending;
+
+    // The UTF-8 key table of a wide index (the U8 entry points' result strings): every key encoded
+    // once (ngs_utf8.h: the decoder's inverse, so an indexU8 key comes back as the bytes indexed),
+    // NUL-terminated, and its byte offsets on each replica's device for k_pack's pointer mode. Built
+    // by the first U8 call (u8_keys, under the shared lock beside other searches): W-only callers
+    // pay nothing. The device arrays are the replicas' (Replica::owned).
+    struct U8Keys {
+        std::once_flag once;
+        bool ok = false;
+        std::vector<char> bytes;             // key_bytes8
+        std::vector<uint64_t> off;           // n_keys + 1 byte offsets
+        std::vector<const uint64_t*> d_off;  // per replica
+    } u8;
     uint64_t next_ticket = 1;
 
     ~Library() {
@@ -1087,6 +1107,31 @@ bool ensure_outputs(Context& c, size_t B, size_t stride) {
     return true;
 }
 
+// The U8 batch's staging on the device: its UTF-8 bytes, its B + 1 byte offsets and the
+// decoder's scratch. (Replaced only between calls: the context's stream is idle then.)
+bool ensure_u8(Context& c, size_t B, size_t bytes) {
+    if (bytes > c.u8cap || !c.d_u8) {
+        if (c.d_u8) hipFree(c.d_u8);
+        c.d_u8 = nullptr;
+        c.u8cap = 0;
+        const size_t nb = std::max<size_t>(bytes, 1 << 16);
+        if (!dev_alloc(&c.d_u8, nb)) return false;
+        c.u8cap = nb;
+    }
+    if (B > c.u8ncap || !c.d_u8off) {
+        if (c.d_u8off) hipFree(c.d_u8off);
+        if (c.d_u8temp) hipFree(c.d_u8temp);
+        c.d_u8off = nullptr;
+        c.d_u8temp = nullptr;
+        c.u8ncap = 0;
+        const size_t nb = std::max<size_t>(B, 1024);
+        c.u8temp_bytes = utf8_temp_bytes((uint32_t)nb);
+        if (!dev_alloc(&c.d_u8off, nb + 1) || !HIP_CHECK(hipMalloc(&c.d_u8temp, c.u8temp_bytes))) return false;
+        c.u8ncap = nb;
+    }
+    return true;
+}
+
 bool ensure_general(const Replica& R, Context& c, hipStream_t s) {
     if (c.gen.G) return true;
     const DevIndex& X = R.dev;
@@ -1491,18 +1536,28 @@ struct HostChunk {
     // pointer mode (pcs != 0): records go out as result pointers pbase + key_off[key] * pcs
     uint64_t pbase = 0;
     uint32_t pcs = 0;
+    // ... through these key offsets (the index's own, or the UTF-8 key table's)
+    const uint64_t* d_koff = nullptr;
+    const uint64_t* h_koff = nullptr;
 };
 
 // Queues chunk [q0, q0 + B) on context c: the queries packed into pinned staging, one H2D copy
 // (two for large chunks), the search kernels. Nothing waits.
+// u8 (CharT = char on a wide index): the queries are UTF-8; their bytes and byte offsets are
+// copied in as they are and decoded on the call's stream into the context's query buffer
+// (launch_utf8_decode), which the pipeline then reads like a W batch. Result pointers go into the
+// UTF-8 key table.
 template <typename CharT>
 bool queue_host_chunk(Library& L, Replica& R, Context& c, const CharT* const* queries, uint32_t q0, uint32_t B,
-                      float thr, uint32_t Lm, HostChunk& h, uint64_t pbase) {
+                      float thr, uint32_t Lm, HostChunk& h, uint64_t pbase, const Library::U8Keys* u8,
+                      size_t replica) {
     constexpr size_t cs = sizeof(CharT);
     const size_t stride = Lm;
     h = HostChunk{};
     h.pbase = pbase;
     h.pcs = pbase ? (uint32_t)cs : 0u;
+    h.d_koff = u8 ? u8->d_off[replica] : R.dev.key_off;
+    h.h_koff = u8 ? u8->off.data() : L.host.key_off.data();
     h.c = &c;
     h.q0 = q0;
     h.B = B;
@@ -1521,7 +1576,8 @@ bool queue_host_chunk(Library& L, Replica& R, Context& c, const CharT* const* qu
     // all through the context's latency block [statistics | results | offsets, bytes]
     h.block = sizeof(uint32_t) * (B + 1 + 2 * (size_t)B * stride);
     const size_t qspace = sizeof(uint64_t) * (B + 1) + qbytes;
-    h.small = B <= kSmallBatch && h.block <= kSmallBlock && qspace <= kSmallQ;
+    h.small = !u8 && B <= kSmallBatch && h.block <= kSmallBlock && qspace <= kSmallQ;
+    uint64_t sbytes = qbytes;  // bytes of the batch as the pipeline reads it
     bool ok;
     if (h.small) {
         uint8_t* hq = c.h_sio + kSioStats + kSmallBlock;
@@ -1544,9 +1600,20 @@ bool queue_host_chunk(Library& L, Replica& R, Context& c, const CharT* const* qu
                 if (queries[q0 + i]) std::memcpy(hr + ho[i], queries[q0 + i], ho[i + 1] - ho[i]);
         });
         ht.mark(kHpPack, "pack queries");
-        ok = ensure_queries(c, B, qbytes) && ensure_outputs(c, B, stride) &&
-             HIP_CHECK(hipMemcpyAsync(c.d_raw, c.h_raw.p, qbytes, hipMemcpyHostToDevice, c.stream)) &&
-             HIP_CHECK(hipMemcpyAsync(c.d_off, ho, sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, c.stream));
+        if (u8) {
+            // at most one unit per byte: 4 x bytes always holds the decoded batch (k_prep's *oflow
+            // still guards the buffer)
+            sbytes = 4 * qbytes;
+            ok = ensure_queries(c, B, sbytes) && ensure_outputs(c, B, stride) && ensure_u8(c, B, qbytes) &&
+                 HIP_CHECK(hipMemcpyAsync(c.d_u8, c.h_raw.p, qbytes, hipMemcpyHostToDevice, c.stream)) &&
+                 HIP_CHECK(hipMemcpyAsync(c.d_u8off, ho, sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, c.stream)) &&
+                 HIP_CHECK(launch_utf8_decode(c.d_u8, c.d_u8off, B, reinterpret_cast<uint32_t*>(c.d_raw), c.qcap / 4,
+                                              c.d_off, c.d_u8temp, c.u8temp_bytes, c.stream));
+        } else {
+            ok = ensure_queries(c, B, qbytes) && ensure_outputs(c, B, stride) &&
+                 HIP_CHECK(hipMemcpyAsync(c.d_raw, c.h_raw.p, qbytes, hipMemcpyHostToDevice, c.stream)) &&
+                 HIP_CHECK(hipMemcpyAsync(c.d_off, ho, sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, c.stream));
+        }
         h.d_raw = c.d_raw;
         h.d_off = c.d_off;
         h.d_n = c.d_n;
@@ -1554,7 +1621,7 @@ bool queue_host_chunk(Library& L, Replica& R, Context& c, const CharT* const* qu
         h.d_s = c.d_s;
     }
     if (!ok) return false;
-    if (queue_search(L, R, c, h.d_raw, h.d_off, B, qbytes, thr, Lm, (uint32_t)stride, h.d_n, h.d_k, h.d_s, c.stream,
+    if (queue_search(L, R, c, h.d_raw, h.d_off, B, sbytes, thr, Lm, (uint32_t)stride, h.d_n, h.d_k, h.d_s, c.stream,
                      h.P, h.small) != 0)
         return false;
     ht.mark(kHpQueue, "copy in + queue kernels");
@@ -1596,7 +1663,7 @@ bool finish_host_chunk(Library& L, Replica& R, HostChunk& h, uint32_t Lm, std::v
             sc.insert(sc.end(), hs + (size_t)i * stride, hs + (size_t)i * stride + hn[i]);
         }
         if (h.pcs) {  // a few records: their pointers made here
-            const uint64_t* koff = L.host.key_off.data();
+            const uint64_t* koff = h.h_koff;
             std::vector<uint64_t> ptr(k.size());
             for (size_t i = 0; i < k.size(); ++i) ptr[i] = h.pbase + koff[k[i]] * h.pcs;
             emit(static_cast<const void*>(ptr.data()), sc.data(), (uint32_t)k.size(), last, (uint32_t)k.size());
@@ -1610,7 +1677,7 @@ bool finish_host_chunk(Library& L, Replica& R, HostChunk& h, uint32_t Lm, std::v
     uint64_t* pp = h.pcs ? reinterpret_cast<uint64_t*>(c.d_pk) : nullptr;
     if (!HIP_CHECK(hipMemsetAsync(c.d_n + B, 0, sizeof(uint32_t), c.stream)) ||
         !HIP_CHECK(launch_pack(c.d_n, c.d_k, c.d_s, B, (uint32_t)stride, c.d_pos, c.d_pk, c.d_ps, c.d_ptemp,
-                               c.ptemp_bytes, c.stream, R.dev.key_off, h.pbase, h.pcs, pp)) ||
+                               c.ptemp_bytes, c.stream, h.d_koff, h.pbase, h.pcs, pp)) ||
         !c.h_res.grow(sizeof(uint32_t) * (B + 1)) ||
         !HIP_CHECK(hipMemcpyAsync(c.h_res.p, c.d_pos, sizeof(uint32_t) * (B + 1), hipMemcpyDeviceToHost, c.stream)) ||
         !HIP_CHECK(hipStreamSynchronize(c.stream)))
@@ -1672,7 +1739,8 @@ size_t host_chunk(uint32_t nq, uint32_t Lm) {
 // each chunk's records, in query order, to emit(keys, scores, n).
 template <typename CharT, class Emit>
 bool host_search_chunks(Library& L, Replica& R, const CharT* const* queries, uint32_t nq, float thr, uint32_t Lm,
-                        std::vector<uint32_t>& counts, Emit&& emit, uint64_t pbase = 0) {
+                        std::vector<uint32_t>& counts, Emit&& emit, uint64_t pbase = 0,
+                        const Library::U8Keys* u8 = nullptr, size_t replica = 0) {
     counts.assign(nq, 0);
     if (Lm == 0 || nq == 0) return true;
     if (!HIP_CHECK(hipSetDevice(R.device))) return false;
@@ -1691,7 +1759,7 @@ bool host_search_chunks(Library& L, Replica& R, const CharT* const* queries, uin
         // queue chunk k, then complete chunk k - 1 while k runs
         if (k < n_chunks) {
             const uint32_t q0 = (uint32_t)(k * chunk), B = (uint32_t)std::min<size_t>(chunk, nq - q0);
-            ok = queue_host_chunk(L, R, *ctx[k & 1], queries, q0, B, thr, Lm, fl[k & 1], pbase);
+            ok = queue_host_chunk(L, R, *ctx[k & 1], queries, q0, B, thr, Lm, fl[k & 1], pbase, u8, replica);
             if (!ok) break;
         }
         if (pending) ok = finish_host_chunk(L, R, fl[(k - 1) & 1], Lm, counts, k == n_chunks, emit);
@@ -1791,14 +1859,15 @@ void set_valid(Library& L, const char* chars, int n) {
 // result strings point into the index's own key storage (valid until dispose, hpp:443-447)
 template <typename CharT>
 uint32_t marshal(const Library& L, const std::vector<uint32_t>& keys, const std::vector<float>& sc,
-                 CharT*** results, float** scores) {
+                 CharT*** results, float** scores, const Library::U8Keys* u8 = nullptr) {
     const size_t n = keys.size();
     if (scores) *scores = new float[n];
     *results = new CharT*[n];
     CharT** res = *results;
     float* out_s = scores ? *scores : nullptr;
-    char* base = const_cast<char*>(L.host.key_bytes.data());
-    const uint64_t* koff = L.host.key_off.data();
+    // (u8, CharT = char: the strings of the UTF-8 key table of a wide index)
+    char* base = const_cast<char*>(u8 ? u8->bytes.data() : L.host.key_bytes.data());
+    const uint64_t* koff = u8 ? u8->off.data() : L.host.key_off.data();
     auto fill = [&](size_t a, size_t b) {  // key_off is gathered at random: memory-latency bound
         for (size_t i = a; i < b; ++i) {
             res[i] = reinterpret_cast<CharT*>(base + koff[keys[i]] * sizeof(CharT));
@@ -2075,6 +2144,53 @@ uint32_t split_direct(Library& L, const CharT* const* queries, uint32_t nq, floa
     return (uint32_t)sum;
 }
 
+// A batch on the first replica, marshalled as the chunks finish, straight into the caller's
+// arrays. One chunk (the common case): the arrays at the exact size, filled from the pinned
+// read-back; several chunks: at the batch's capacity (nq x limit entries; only the pages written
+// are touched). Pointer mode: k_pack writes each record as its result pointer into the host key
+// bytes (key_off gathered on the device), so marshalling is two parallel copies. u8: UTF-8
+// queries on a wide index, decoded on the device, the pointers into the UTF-8 key table.
+template <typename CharT>
+uint32_t direct_batch(Library& L, const CharT* const* queries, uint32_t nq, float thr, uint32_t Lm, uint32_t* counts,
+                      CharT*** results, float** scores, HostTimer& ht, const Library::U8Keys* u8 = nullptr) {
+    std::vector<uint32_t> cnt;
+    CharT** res = nullptr;
+    float* out_s = nullptr;
+    size_t off = 0, cap = 0;
+    const uint64_t pbase = (uint64_t)(uintptr_t)(u8 ? u8->bytes.data() : L.host.key_bytes.data());
+    static_assert(sizeof(CharT*) == sizeof(uint64_t), "result pointers are 64-bit");
+    const bool ok = host_search_chunks(L, *L.reps.front(), queries, nq, thr, Lm, cnt,
+                                       [&](const void* recs, const float* sc, uint32_t n, bool last,
+                                           uint32_t chunk_total) {
+        if (!res) {
+            cap = (off == 0 && last) ? std::max<size_t>(chunk_total, 1) : (size_t)nq * Lm;
+            res = new CharT*[cap];
+            out_s = scores ? new float[cap] : nullptr;
+        }
+        const uint64_t* p = static_cast<const uint64_t*>(recs);
+        parallel_ranges(n, size_t(1) << 16, [&](size_t a, size_t e) {
+            std::memcpy(res + off + a, p + a, (e - a) * sizeof(uint64_t));
+            if (out_s) std::memcpy(out_s + off + a, sc + a, (e - a) * sizeof(float));
+        });
+        off += n;
+    }, pbase, u8, 0);
+    if (ok && !res) {  // no chunk ran (cannot happen with nq >= kSmallBatch): empty arrays
+        res = new CharT*[1];
+        out_s = scores ? new float[1] : nullptr;
+    }
+    if (!ok) {
+        delete[] res;
+        delete[] out_s;
+        return 0;
+    }
+    ht.mark(kHpCall, "search + marshal (chunks)");
+    g_host_phase[kHpCalls].fetch_add(1, std::memory_order_relaxed);
+    std::copy(cnt.begin(), cnt.end(), counts);
+    *results = res;
+    if (scores) *scores = out_s;
+    return (uint32_t)off;
+}
+
 template <typename CharT>
 uint32_t batch_query(uint32_t handle, const CharT* const* queries, uint32_t nq, float thr, uint32_t limit,
                      uint32_t* counts, CharT*** results, float** scores) {
@@ -2089,48 +2205,8 @@ uint32_t batch_query(uint32_t handle, const CharT* const* queries, uint32_t nq, 
     HostTimer ht;
     const uint32_t Lm = effective_limit(*L, limit);
     const bool one_replica = L->split.size() <= 1 || nq / split_min() <= 1;
-    if (one_replica && Lm && (uint64_t)nq * Lm <= kDirectMax && nq >= kSmallBatch) {
-        // marshalled as the chunks finish, straight into the caller's arrays. One chunk (the
-        // common case): the arrays at the exact size, filled from the pinned read-back; several
-        // chunks: at the batch's capacity (nq x limit entries; only the pages written are touched)
-        CharT** res = nullptr;
-        float* out_s = nullptr;
-        size_t off = 0, cap = 0;
-        // pointer mode: k_pack writes each record as its result pointer into the host key bytes
-        // (key_off gathered on the device), so marshalling is two parallel copies
-        const uint64_t pbase = (uint64_t)(uintptr_t)L->host.key_bytes.data();
-        static_assert(sizeof(CharT*) == sizeof(uint64_t), "result pointers are 64-bit");
-        const bool ok = host_search_chunks(*L, *L->reps.front(), queries, nq, thr, Lm, cnt,
-                                           [&](const void* recs, const float* sc, uint32_t n, bool last,
-                                               uint32_t chunk_total) {
-            if (!res) {
-                cap = (off == 0 && last) ? std::max<size_t>(chunk_total, 1) : (size_t)nq * Lm;
-                res = new CharT*[cap];
-                out_s = scores ? new float[cap] : nullptr;
-            }
-            const uint64_t* p = static_cast<const uint64_t*>(recs);
-            parallel_ranges(n, size_t(1) << 16, [&](size_t a, size_t e) {
-                std::memcpy(res + off + a, p + a, (e - a) * sizeof(uint64_t));
-                if (out_s) std::memcpy(out_s + off + a, sc + a, (e - a) * sizeof(float));
-            });
-            off += n;
-        }, pbase);
-        if (ok && !res) {  // no chunk ran (cannot happen with nq >= kSmallBatch): empty arrays
-            res = new CharT*[1];
-            out_s = scores ? new float[1] : nullptr;
-        }
-        if (!ok) {
-            delete[] res;
-            delete[] out_s;
-            return 0;
-        }
-        ht.mark(kHpCall, "search + marshal (chunks)");
-        g_host_phase[kHpCalls].fetch_add(1, std::memory_order_relaxed);
-        std::copy(cnt.begin(), cnt.end(), counts);
-        *results = res;
-        if (scores) *scores = out_s;
-        return (uint32_t)off;
-    }
+    if (one_replica && Lm && (uint64_t)nq * Lm <= kDirectMax && nq >= kSmallBatch)
+        return direct_batch(*L, queries, nq, thr, Lm, counts, results, scores, ht);
     if (Lm && nq >= kSmallBatch && !one_replica) {
         const uint32_t n = split_direct(*L, queries, nq, thr, Lm, counts, results, scores);
         if (n != kNoDirect) {
@@ -2144,6 +2220,113 @@ uint32_t batch_query(uint32_t handle, const CharT* const* queries, uint32_t nq, 
     const uint32_t n = marshal(*L, keys, sc, results, scores);
     ht.mark(kHpCall, "search + marshal");
     if (nq >= kSmallBatch) g_host_phase[kHpCalls].fetch_add(1, std::memory_order_relaxed);
+    return n;
+}
+
+// ---- UTF-8 front end (indexU8 / searchU8 / scoreU8 / the U8 batch calls) ----
+
+// NUL-terminated UTF-8 strings decoded (ngs_utf8.h) into one buffer of NUL-terminated UTF-32
+// strings, on the host worker threads; a null string stays null.
+struct DecodedStrings {
+    std::vector<uint32_t> units;
+    std::vector<const uint32_t*> ptr;
+};
+void decode_strings(const char* const* strs, uint64_t n, DecodedStrings& D) {
+    std::vector<uint64_t> off(n + 1, 0);  // room per string: a unit takes at least a byte, and the NUL
+    parallel_ranges(n, 8192, [&](size_t a, size_t e) {
+        for (size_t i = a; i < e; ++i) off[i + 1] = strs[i] ? std::strlen(strs[i]) + 1 : 0;
+    });
+    for (uint64_t i = 0; i < n; ++i) off[i + 1] += off[i];
+    D.units.resize(std::max<uint64_t>(off[n], 1));
+    D.ptr.assign(n, nullptr);
+    parallel_ranges(n, 8192, [&](size_t a, size_t e) {
+        for (size_t i = a; i < e; ++i) {
+            if (!strs[i]) continue;
+            uint32_t* out = D.units.data() + off[i];
+            const size_t u = utf8_decode(reinterpret_cast<const uint8_t*>(strs[i]), off[i + 1] - off[i] - 1, out);
+            out[u] = 0;
+            D.ptr[i] = out;
+        }
+    });
+}
+
+// The library's UTF-8 key table, built by the first call that needs it; null on a HIP failure.
+const Library::U8Keys* u8_keys(Library& L) {
+    Library::U8Keys& T = L.u8;
+    std::call_once(T.once, [&] {
+        const HostIndex& H = L.host;
+        const uint32_t* units = reinterpret_cast<const uint32_t*>(H.key_bytes.data());
+        const size_t nk = H.n_keys;
+        T.off.assign(nk + 1, 0);
+        parallel_ranges(nk, size_t(1) << 14, [&](size_t a, size_t e) {  // (key_off counts the NUL in)
+            for (size_t k = a; k < e; ++k)
+                T.off[k + 1] = utf8_encoded_len(units + H.key_off[k], H.key_off[k + 1] - 1 - H.key_off[k]) + 1;
+        });
+        for (size_t k = 0; k < nk; ++k) T.off[k + 1] += T.off[k];
+        T.bytes.resize(std::max<uint64_t>(T.off[nk], 1));
+        parallel_ranges(nk, size_t(1) << 14, [&](size_t a, size_t e) {
+            for (size_t k = a; k < e; ++k) {
+                uint8_t* out = reinterpret_cast<uint8_t*>(T.bytes.data()) + T.off[k];
+                out[utf8_encode(units + H.key_off[k], H.key_off[k + 1] - 1 - H.key_off[k], out)] = 0;
+            }
+        });
+        // the offsets on every replica's device (the caller's current device kept)
+        int dev = -1;
+        (void)hipGetDevice(&dev);
+        bool ok = true;
+        for (auto& R : L.reps) {
+            uint64_t* d = nullptr;
+            ok = ok && HIP_CHECK(hipSetDevice(R->device)) && dev_alloc(&d, nk + 1);
+            if (d) {
+                std::lock_guard<std::mutex> g(R->kflag_mu);  // (Replica::owned is shared with index_for)
+                R->owned.push_back(d);
+            }
+            ok = ok && HIP_CHECK(hipMemcpy(d, T.off.data(), sizeof(uint64_t) * (nk + 1), hipMemcpyHostToDevice));
+            T.d_off.push_back(d);
+        }
+        if (dev >= 0) (void)hipSetDevice(dev);
+        T.ok = ok;
+    });
+    return T.ok ? &T : nullptr;
+}
+
+// searchU8 / scoreU8 and the U8 batch calls (counts null: one query). The answers are the W
+// call's on the decoded units; the result strings are the UTF-8 key table's. Up to kSmallBatch
+// queries are decoded on the host and take the wide latency path; a larger batch goes up as UTF-8
+// and is decoded on the device (queue_host_chunk), answered by the first replica.
+uint32_t u8_query(uint32_t handle, const char* const* queries, uint32_t nq, float thr, uint32_t limit,
+                  uint32_t* counts, char*** results, float** scores) {
+    const bool single = counts == nullptr;
+    if (counts) std::fill(counts, counts + nq, 0u);
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L || !L->host.indexed || !queries || (single && !queries[0]) || L->host.csize != sizeof(uint32_t)) return 0;
+    const Library::U8Keys* T = u8_keys(*L);
+    if (!T) return 0;
+    BatchGuard bg(batch_mark(L, nq));
+    std::vector<uint32_t> cnt, keys;
+    std::vector<float> sc;
+    HostTimer ht;
+    if (nq <= kSmallBatch) {
+        DecodedStrings D;
+        decode_strings(queries, nq, D);
+        if (!host_search(*L, D.ptr.data(), nq, thr, limit, cnt, keys, sc)) return 0;
+    } else {
+        const uint32_t Lm = effective_limit(*L, limit);
+        if (Lm && (uint64_t)nq * Lm <= kDirectMax)
+            return direct_batch(*L, queries, nq, thr, Lm, counts, results, scores, ht, T);
+        bool ok = host_search_chunks(*L, *L->reps.front(), queries, nq, thr, Lm, cnt,
+                                     [&](const void* recs, const float* s, uint32_t n, bool, uint32_t) {
+            const uint32_t* k = static_cast<const uint32_t*>(recs);
+            keys.insert(keys.end(), k, k + n);
+            sc.insert(sc.end(), s, s + n);
+        }, 0, T, 0);
+        if (!ok) return 0;
+        g_host_phase[kHpCalls].fetch_add(1, std::memory_order_relaxed);
+    }
+    if (counts) std::copy(cnt.begin(), cnt.end(), counts);
+    const uint32_t n = marshal(*L, keys, sc, results, scores, T);
+    ht.mark(kHpCall, "search + marshal (UTF-8)");
     return n;
 }
 
@@ -2289,6 +2472,119 @@ NGS_API void disposeW(uint32_t handle) { dispose(handle); }
 NGS_API uint64_t getSizeW(uint32_t handle) { return getSize(handle); }
 
 NGS_API uint64_t getLibSizeW(uint32_t handle) { return getLibSize(handle); }
+
+// ---- UTF-8 API on wide indexes (include/ngram_search.h): strings in and out are UTF-8, the
+// index and the search are the wide ones.
+
+NGS_API uint32_t indexU8(char** words, uint64_t size, uint16_t rowSize, float* weight, uint16_t gSize) {
+    if (gSize < 1 || gSize > kMaxGramSize) return 0;
+    DecodedStrings D;
+    if (words) decode_strings(words, size, D);
+    return new_library([&](HostIndex& H) {
+        build_index_w(H, words ? D.ptr.data() : nullptr, size, rowSize, weight, gSize);
+    });
+}
+
+NGS_API uint32_t searchU8(uint32_t handle, const char* query, char*** results, float threshold, uint32_t limit) {
+    return u8_query(handle, &query, 1, threshold, limit, nullptr, results, nullptr);
+}
+
+NGS_API uint32_t scoreU8(uint32_t handle, const char* query, char*** results, float** scores, float threshold,
+                         uint32_t limit) {
+    return u8_query(handle, &query, 1, threshold, limit, nullptr, results, scores);
+}
+
+NGS_API uint32_t scoreBatchU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                              uint32_t limit, uint32_t* counts, char*** results, float** scores) {
+    if (!counts) return 0;
+    return u8_query(handle, queries, nQueries, threshold, limit, counts, results, scores);
+}
+
+NGS_API uint32_t searchBatchU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                               uint32_t limit, uint32_t* counts, char*** results) {
+    if (!counts) return 0;
+    return u8_query(handle, queries, nQueries, threshold, limit, counts, results, nullptr);
+}
+
+NGS_API const char* ngsKeyU8(uint32_t handle, uint32_t keyId) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L || !L->host.indexed || keyId >= L->host.n_keys || L->host.csize != sizeof(uint32_t)) return nullptr;
+    const Library::U8Keys* T = u8_keys(*L);
+    return T ? T->bytes.data() + T->off[keyId] : nullptr;
+}
+
+NGS_API int ngsUtf8Decode(const uint8_t* dBytes, const uint64_t* dOffsets, uint32_t n, uint8_t* dOut,
+                          uint64_t outCapBytes, uint64_t* dOutOffsets, void* stream) {
+    if (!dOffsets || !dOutOffsets || (n && !dBytes) || (outCapBytes >= 4 && !dOut) || ((uintptr_t)dOut & 3u))
+        return -3;
+    // the scan's scratch per (device, stream), kept as ngsPackResults keeps its own
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> temp;
+    int dev = 0;
+    if (!HIP_CHECK(hipGetDevice(&dev))) return -4;
+    std::lock_guard<std::mutex> g(mu);
+    auto& t = temp[{dev, (hipStream_t)stream}];
+    const size_t need = utf8_temp_bytes(n);
+    if (need > t.second) {
+        if (t.first && !HIP_CHECK(hipStreamSynchronize((hipStream_t)stream))) return -4;
+        if (t.first) (void)hipFree(t.first);
+        t = {nullptr, 0};
+        if (!HIP_CHECK(hipMalloc(&t.first, std::max<size_t>(need, 1 << 16)))) return -4;
+        t.second = std::max<size_t>(need, 1 << 16);
+    }
+    return HIP_CHECK(launch_utf8_decode(dBytes, dOffsets, n, reinterpret_cast<uint32_t*>(dOut), outCapBytes / 4,
+                                        dOutOffsets, t.first, t.second, (hipStream_t)stream))
+               ? 0
+               : -4;
+}
+
+NGS_API int ngsSearchDeviceU8(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                              uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
+                              uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L) return -1;
+    if (!L->host.indexed) return -2;
+    if (L->host.csize != sizeof(uint32_t)) return -3;
+    const uint32_t Lm = effective_limit(*L, limit);
+    if (!dQueryOffsets || !dCounts || (nQueries && Lm && (!dKeys || !dScores || outStride < Lm))) return -3;
+    int cur = L->device;
+    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
+    Replica* Rp = L->replica_at(cur);
+    if (!Rp) return -3;
+    Replica& R = *Rp;
+    hipStream_t s = (hipStream_t)stream;
+    BatchGuard bg(L);
+    if (Lm == 0 || nQueries == 0) {
+        return HIP_CHECK(hipMemsetAsync(dCounts, 0, sizeof(uint32_t) * nQueries, s)) &&
+                       HIP_CHECK(hipStreamSynchronize(s))
+                   ? 0
+                   : -4;
+    }
+    // the batch's UTF-8 byte count bounds its units: the context's query buffer takes 4 bytes each
+    uint64_t ends[2] = {0, 0};
+    if (!HIP_CHECK(hipMemcpyAsync(&ends[0], dQueryOffsets, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) ||
+        !HIP_CHECK(hipMemcpyAsync(&ends[1], dQueryOffsets + nQueries, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) ||
+        !HIP_CHECK(hipStreamSynchronize(s)))
+        return -4;
+    if (ends[1] < ends[0]) return -3;
+    const uint64_t qbytes = 4 * (ends[1] - ends[0]);
+    std::unique_ptr<Context> c = R.acquire();
+    if (!c) return -4;
+    int rc = -4;
+    if (ensure_queries(*c, nQueries, qbytes) && ensure_u8(*c, nQueries, 0) &&
+        HIP_CHECK(launch_utf8_decode(dQueryBytes, dQueryOffsets, nQueries, reinterpret_cast<uint32_t*>(c->d_raw),
+                                     c->qcap / 4, c->d_off, c->d_u8temp, c->u8temp_bytes, s)))
+        rc = device_search(*L, R, *c, c->d_raw, c->d_off, nQueries, qbytes, threshold, Lm, outStride, dCounts, dKeys,
+                           dScores, s);
+    if (rc == kRetryQcap) {  // cannot happen: the buffer was sized for the batch
+        rc = -5;
+        t_last_error = kErrQueryBuffer;
+    }
+    R.give_back(std::move(c));
+    return rc;
+}
 
 NGS_API int ngsSetDevices(const int* devices, int n) {
     if (n < 0 || (n > 0 && !devices)) return -(int)hipErrorInvalidValue;

@@ -331,3 +331,58 @@ class WideStringIndex(StringIndex):
         if self.handle:
             _native.lib().disposeW(self.handle)
             self.handle = 0
+
+
+# ---- UTF-8 strings on a wide index (indexU8 extension) ----------------------------------
+def _u8(s) -> bytes:
+    """str -> UTF-8 (lone surrogates U+DC80..DCFF back to the bytes they stand for); bytes as they are."""
+    return s if isinstance(s, (bytes, bytearray)) else s.encode("utf-8", "surrogateescape")
+
+
+def _u8string(p) -> str:
+    return C.string_at(p).decode("utf-8", "surrogateescape")
+
+
+def utf8_decode_device(d_bytes: int, d_offsets: int, n: int, d_out: int, out_cap_bytes: int, d_out_offsets: int,
+                       stream: int = 0) -> None:
+    """ngsUtf8Decode on raw device pointers: n UTF-8 strings (absolute byte offsets) -> UTF-32
+    characters in d_out and their byte offsets (from 0) in d_out_offsets, queued on `stream`."""
+    rc = _native.lib().ngsUtf8Decode(d_bytes, d_offsets, n, d_out, out_cap_bytes, d_out_offsets, stream or None)
+    if rc:
+        raise RuntimeError(f"ngsUtf8Decode failed: {rc}")
+
+
+class Utf8StringIndex(WideStringIndex):
+    """indexU8 / searchU8 / scoreU8 / scoreBatchU8: a wide index driven with UTF-8. Words and
+    queries are str (encoded with 'utf-8', 'surrogateescape') or bytes (taken as they are);
+    results are str decoded the same way, so bytes that are not UTF-8 come back as U+DC80..DCFF."""
+
+    _INDEX = "indexU8"
+    _RES = C.POINTER(C.POINTER(C.c_char))
+    _fn = {"search": "searchU8", "score": "scoreU8", "release": "release", "scoreBatch": "scoreBatchU8",
+           "key": "ngsKeyU8"}
+
+    @staticmethod
+    def _words(words):
+        arr = (C.c_char_p * max(1, len(words)))()
+        for i, w in enumerate(words):
+            arr[i] = None if w is None else _u8(w)
+        return arr
+
+    @staticmethod
+    def _index(L, arr, n, row_size, w, gram_size):
+        return L.indexU8(arr, n, row_size, w, gram_size)
+
+    _q = staticmethod(_u8)
+    _string = staticmethod(_u8string)
+
+    def _queries(self, queries):
+        return (C.c_char_p * max(1, len(queries)))(*[_u8(q) for q in queries])
+
+    def search_device_u8(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int, out_stride: int,
+                         d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> None:
+        """ngsSearchDeviceU8: search_device with UTF-8 query bytes and offsets."""
+        rc = _native.lib().ngsSearchDeviceU8(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
+                                             d_counts, d_keys, d_scores, stream or None)
+        if rc:
+            raise RuntimeError(f"ngsSearchDeviceU8 failed: {rc}")
