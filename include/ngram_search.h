@@ -53,7 +53,8 @@ NGS_API uint32_t search(uint32_t handle, const char* query, char*** results, flo
 NGS_API uint32_t score(uint32_t handle, const char* query, char*** results, float** scores,
                        float threshold, uint32_t limit);
 
-/* dllmain.cpp:98. delete[]s arrays returned by search/score/searchBatch/scoreBatch. */
+/* dllmain.cpp:98. delete[]s arrays returned by search/score/searchBatch/scoreBatch. Either may be
+ * NULL; scoreBatchSim's third array goes through the float argument: release(handle, NULL, sims). */
 NGS_API void release(uint32_t handle, char** results, float* scores);
 
 /* dllmain.cpp:110. Frees the index (host and device). Unknown handles are ignored. */
@@ -244,6 +245,69 @@ NGS_API int ngsServe(uint32_t handle, int enable);
 NGS_API int ngsPackResults(const uint32_t* dCounts, const uint32_t* dKeys, const float* dScores, uint32_t n,
                            uint32_t stride, uint32_t* dOffsets, uint32_t* dRecords, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Edit-distance similarity and re-ranking of a result block on the device (not in the
+ * reference). The search's score (weight x shared grams / query grams) is a candidate filter;
+ * these stages verify the candidates where they lie, in HBM, as stream-ordered stages behind
+ * ngsSearchDevice / ngsSearchDeviceAsync (after its Wait) on the caller's stream.
+ *
+ * The similarity of a record (query i, key k):
+ *   Q  = the query normalised as the search does it: every character through escapeBlank with the
+ *        handle's validChar set at the time of the call, blanks trimmed at both ends, toupper;
+ *        m = |Q| in characters (bytes; UTF-32 units on a wide index);
+ *   T  = a normalised term of the index (built with the default set, L = |T| >= 1); the terms of
+ *        key k are those of every (term, key) pair the index holds, whatever the weight;
+ *   d  = the unit-cost Levenshtein distance of Q and T (insert, delete, substitute; global);
+ *   sim(Q, T) = 1.0f - (float)d / (float)max(m, L), in fp32 (one correctly rounded division, one
+ *        subtraction: numpy.float32 arithmetic gives the same bits);
+ *   sim(record) = the largest sim(Q, T) over the terms T of key k: a query that matched an alias
+ *        gets the alias's similarity, not the master string's.
+ * A wildcard query (raw length 0, or the single character '*') has sim 1.0f on every record,
+ * whatever its key id. Otherwise a query of more than 4,096 normalised characters, or a key id
+ * >= ngsNumKeys, has sim -1.0f ("not computed"; nothing is read through the id), which filters and
+ * orders like any other value. A count above `stride` is read as `stride`.
+ * The query bytes and offsets have exactly ngsSearchDevice's layout: pass the same buffers (for a
+ * wide handle UTF-32 units and offsets in multiples of 4, e.g. those ngsUtf8Decode wrote).
+ * Both calls use the replica on the caller's current device, queue their kernels on `stream` and
+ * return without waiting. (On an index whose keys have one pair each, the first call on a replica
+ * builds a 4-byte-per-key map on the device and waits for that once.) Arguments are checked before
+ * anything else: -3 bad argument, then -1 bad handle, -2 un-built index, -3 no replica on the
+ * current device, -4 HIP error.
+ * ------------------------------------------------------------------------------------ */
+
+/* dSim[i*stride + r] for r < dCounts[i]: the similarity above of query i and key dKeys[i*stride + r].
+ * Reads dCounts/dKeys, writes only dSim. Stream-ordered on `stream`, no host wait.
+ * 0, -1 bad handle, -2 un-built, -3 bad argument / no replica on the current device, -4 HIP error. */
+NGS_API int ngsSimilarityDevice(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                uint32_t nQueries, uint32_t stride, const uint32_t* dCounts,
+                                const uint32_t* dKeys, float* dSim, void* stream);
+
+/* ngsSimilarityDevice, then per query: records with sim < minSimilarity are dropped, the rest put in
+ * order of (sim descending, previous position ascending). dCounts, dKeys, dScores and dSim are
+ * rewritten in place (entries past the new count are unspecified). stride <= kRerankMaxStride (4,096),
+ * minSimilarity not NaN, else -3. Stream-ordered, no host wait. */
+NGS_API int ngsRerankDevice(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                            uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys,
+                            float* dScores, float* dSim, float minSimilarity, void* stream);
+
+/* scoreBatch / scoreBatchW / scoreBatchU8 followed by the re-rank: query i's counts[i] results are
+ * those of the search that pass minSimilarity, in order of (sim descending, the search's order
+ * ascending); *sims is a third flat new[]'d array beside *results and *scores, sims[j] belonging to
+ * results[j]. Free it with release(handle, NULL, sims) (release delete[]s a float array), the other
+ * two as usual. The effective limit min(limit or 2^31-1, ngsNumKeys) must not exceed 4,096: above it
+ * the call fails (returns 0, counts zeroed, outputs untouched) and ngsLastError() is
+ * NGS_ERR_RERANK_LIMIT. Unknown handle, un-built index, width mismatch, NaN minSimilarity: 0, counts
+ * zeroed, outputs untouched. The first replica answers. */
+NGS_API uint32_t scoreBatchSim(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                               uint32_t limit, float minSimilarity, uint32_t* counts, char*** results,
+                               float** scores, float** sims);
+NGS_API uint32_t scoreBatchSimW(uint32_t handle, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                uint32_t limit, float minSimilarity, uint32_t* counts, wchar_t*** results,
+                                float** scores, float** sims);
+NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                                 uint32_t limit, float minSimilarity, uint32_t* counts, char*** results,
+                                 float** scores, float** sims);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);
@@ -279,13 +343,15 @@ typedef struct {
 } ngs_stats;
 NGS_API int ngsSetTiming(uint32_t handle, int enable);
 /* The last failure of a call on this thread (0: none); clear != 0 resets it. A HIP error code, or
- * NGS_ERR_INTERNAL (a kernel reported an internal error, the -5 of the device entry points) or
- * NGS_ERR_QUERY_BUFFER (a batch outgrew the normalised-query buffer on its rerun). A batch split
+ * NGS_ERR_INTERNAL (a kernel reported an internal error, the -5 of the device entry points),
+ * NGS_ERR_QUERY_BUFFER (a batch outgrew the normalised-query buffer on its rerun) or
+ * NGS_ERR_RERANK_LIMIT (scoreBatchSim* with an effective limit above 4,096). A batch split
  * across replicas hands a replica thread's failure to the calling thread. The reference entry
  * points answer 0 on failure, indistinguishable from "no results": a caller that must tell them
  * apart asks here afterwards. */
 #define NGS_ERR_INTERNAL 0x10001
 #define NGS_ERR_QUERY_BUFFER 0x10002
+#define NGS_ERR_RERANK_LIMIT 0x10003 /* scoreBatchSim*: the effective limit is above 4,096 */
 NGS_API int ngsLastError(int clear);
 NGS_API int ngsLastStats(uint32_t handle, ngs_stats* out);
 

@@ -164,6 +164,20 @@ def lib():
     if hasattr(L, "ngsPackResults"):
         L.ngsPackResults.restype = C.c_int
         L.ngsPackResults.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "ngsSimilarityDevice"):  # (experiment builds of older sources lack the similarity stage)
+        L.ngsSimilarityDevice.restype = C.c_int
+        L.ngsSimilarityDevice.argtypes = [u32, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]
+        L.ngsRerankDevice.restype = C.c_int
+        L.ngsRerankDevice.argtypes = [u32, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, f32, C.c_void_p]
+        PF = C.POINTER(C.POINTER(f32))
+        L.scoreBatchSim.restype = u32
+        L.scoreBatchSim.argtypes = [u32, C.POINTER(cp), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF, PF]
+        L.scoreBatchSimW.restype = u32
+        L.scoreBatchSimW.argtypes = [u32, C.POINTER(W), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PW), PF, PF]
+        L.scoreBatchSimU8.restype = u32
+        L.scoreBatchSimU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF, PF]
     if hasattr(L, "ngsServeState"):
         L.ngsServeState.restype = C.c_int
         L.ngsServeState.argtypes = [u32]

@@ -28,6 +28,7 @@
 #include "ngs_build.h"
 #include "ngs_index.h"
 #include "ngs_kernels.h"
+#include "ngs_sim.h"
 #include "ngs_utf8.h"
 
 namespace ngs {
@@ -54,6 +55,7 @@ thread_local int t_last_error = 0;
 // failures that are not HIP errors (include/ngram_search.h: NGS_ERR_*)
 constexpr int kErrInternal = 0x10001;     // a kernel reported an internal error (finish_search -5)
 constexpr int kErrQueryBuffer = 0x10002;  // the batch outgrew the normalised-query buffer twice
+constexpr int kErrRerankLimit = 0x10003;  // scoreBatchSim*: the effective limit is above kRerankMaxStride
 
 bool hip_ok(hipError_t e, const char* what) {
     if (e == hipSuccess) return true;
@@ -427,6 +429,10 @@ struct Replica {
     hipEvent_t main_ev = nullptr;
     bool main_rec = false;
     hipStream_t shared_side = nullptr;  // one side stream for every context (made under main_mu)
+    // the similarity stage's key -> term map of an index whose keys have one pair each (no kt_off):
+    // built from tk on the device by the first similarity call on the replica (sim_key_term)
+    std::mutex sim_mu;
+    const uint32_t* key_term = nullptr;
 
     // the index as the kernels of a search under `valid` see it (kt_flag for that set); false on a
     // HIP failure
@@ -452,9 +458,13 @@ struct Replica {
         return true;
     }
 
+    // The similarity entry points queue kernels that read the index on the caller's stream and
+    // return: the device is drained before the index arrays go, so dispose() does not free one
+    // under such a kernel (hipFree waits for the device as well; this states it).
     ~Replica() {
         pool.clear();
         hipSetDevice(device);
+        (void)hipDeviceSynchronize();
         if (main_ev) hipEventDestroy(main_ev);
         if (shared_side) hipStreamDestroy(shared_side);
         for (void* p : owned) hipFree(p);
@@ -2365,6 +2375,214 @@ uint32_t new_library(Build&& build) {
     g_libs.emplace(handle, std::move(L));
     return handle;
 }
+
+// ngsSearchDevice on replica R (the caller holds the shared lock and a BatchGuard, and R's device
+// is current): a context from R's pool, the search, the rerun when the batch outgrew the context's
+// normalised-query buffer.
+int search_on_replica(Library& L, Replica& R, const uint8_t* d_raw, const uint64_t* d_off, uint32_t B, float thr,
+                      uint32_t Lm, uint32_t stride, uint32_t* d_n, uint32_t* d_k, float* d_s, hipStream_t s) {
+    if (Lm == 0) {
+        return HIP_CHECK(hipMemsetAsync(d_n, 0, sizeof(uint32_t) * B, s)) && HIP_CHECK(hipStreamSynchronize(s)) ? 0 : -4;
+    }
+    std::unique_ptr<Context> c = R.acquire();
+    if (!c) return -4;
+    // The batch's byte count sizes the normalised-query buffer. A context that has one already
+    // launches without reading it back (a sync before any kernel); k_prep flags a batch that
+    // does not fit and the call reruns after the read-back.
+    int rc = 0;
+    auto read_bytes = [&](uint64_t& qb) -> bool {
+        return HIP_CHECK(hipMemcpyAsync(&qb, d_off + B, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) &&
+               HIP_CHECK(hipStreamSynchronize(s));
+    };
+    uint64_t qbytes = 0;
+    if (B && !c->qcap && !read_bytes(qbytes)) rc = -4;
+    if (!rc) rc = device_search(L, R, *c, d_raw, d_off, B, qbytes, thr, Lm, stride, d_n, d_k, d_s, s);
+    if (rc == kRetryQcap) {
+        rc = read_bytes(qbytes) ? device_search(L, R, *c, d_raw, d_off, B, qbytes, thr, Lm, stride, d_n, d_k, d_s, s) : -4;
+        if (rc == kRetryQcap) {
+            rc = -5;
+            t_last_error = kErrQueryBuffer;
+        }
+    }
+    R.give_back(std::move(c));
+    return rc;
+}
+
+// ---- the similarity stage (ngsSimilarityDevice / ngsRerankDevice / scoreBatchSim*) ----
+
+// The key -> term map of replica R for the similarity kernels: null with ok == true when the index
+// has kt_off / kt_term (they list every key's terms). Otherwise every key has one pair and nothing
+// maps it back: the first call builds key_term[n_keys] from the device's own tk arrays (the host's
+// are released after the upload), synchronously on the null stream like a validChar set's key
+// flags, so that a call on any stream may use it as soon as it is published. Kept until dispose
+// (Replica::owned). R's device is current.
+const uint32_t* sim_key_term(Replica& R, bool& ok) {
+    ok = true;
+    if (R.dev.kt_off) return nullptr;
+    std::lock_guard<std::mutex> g(R.sim_mu);
+    if (R.key_term) return R.key_term;
+    uint32_t* kt = nullptr;
+    ok = dev_alloc(&kt, R.dev.n_keys);
+    if (!ok) return nullptr;
+    {
+        std::lock_guard<std::mutex> o(R.kflag_mu);  // (Replica::owned is shared with index_for)
+        R.owned.push_back(kt);
+    }
+    ok = HIP_CHECK(build_key_term(R.dev, kt, nullptr)) && HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (!ok) return nullptr;
+    R.key_term = kt;
+    return kt;
+}
+
+// the argument checks of the two device entry points, before any handle or device is touched
+bool sim_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint32_t* d_n, const uint32_t* d_k,
+                 const float* d_v) {
+    return d_off && d_n && !(n && stride && (!d_k || !d_v));
+}
+
+// Queues the similarity kernel (and, with `rerank`, the re-rank behind it) on s; nothing waits.
+int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
+                     uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, bool rerank, float min_sim, hipStream_t s) {
+    if (n == 0) return 0;
+    bool ok = true;
+    const uint32_t* key_term = sim_key_term(R, ok);
+    if (!ok) return -4;
+    uint32_t valid[8];
+    {
+        std::lock_guard<std::mutex> g(L.valid_mu);
+        std::memcpy(valid, L.valid, sizeof valid);
+    }
+    if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, d_v, s))) return -4;
+    if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, min_sim, s))) return -4;
+    return 0;
+}
+
+// the entry points' common front: lock held by the caller; the replica on the current device
+int sim_entry(uint32_t handle, Library*& L, Replica*& R) {
+    L = find_lib(handle);
+    if (!L) return -1;
+    if (!L->host.indexed) return -2;
+    int cur = L->device;
+    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
+    R = L->replica_at(cur);
+    return R ? 0 : -3;  // no replica on the caller's device: its buffers and stream belong there
+}
+
+// Device buffers of one scoreBatchSim* call, freed when it returns.
+struct SimBuffers {
+    std::vector<void*> mem;
+    hipStream_t stream = nullptr;
+    template <class T>
+    bool alloc(T** p, size_t n) {
+        if (!dev_alloc(p, n)) return false;
+        mem.push_back(*p);
+        return true;
+    }
+    ~SimBuffers() {
+        if (stream) (void)hipStreamDestroy(stream);
+        for (void* p : mem) (void)hipFree(p);
+    }
+};
+constexpr size_t kSimChunkRecords = size_t(1) << 22;  // records (query x limit) per chunk of a scoreBatchSim* call
+
+// scoreBatchSim / scoreBatchSimW / scoreBatchSimU8, plainly on top of the device stages: the
+// queries packed and uploaded, the search as ngsSearchDevice runs it, ngsRerankDevice's kernels
+// behind it on the same stream, then counts, key ids, scores and sims read back and the result
+// pointers built as marshal() builds every other call's. u8: UTF-8 queries on a wide index
+// (decoded on the host), the strings of the UTF-8 key table. The first replica answers.
+template <typename CharT>
+uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, float thr, uint32_t limit, float min_sim,
+                   uint32_t* counts, CharT*** results, float** scores, float** sims, bool u8) {
+    if (counts) std::fill(counts, counts + nq, 0u);
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    const uint32_t cs = u8 ? (uint32_t)sizeof(uint32_t) : (uint32_t)sizeof(CharT);
+    if (!L || !L->host.indexed || !queries || !counts || !results || !scores || !sims || L->host.csize != cs) return 0;
+    if (min_sim != min_sim) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    const uint32_t Lm = effective_limit(*L, limit);
+    if (Lm > kRerankMaxStride) {
+        t_last_error = kErrRerankLimit;
+        return 0;
+    }
+    const Library::U8Keys* T = u8 ? u8_keys(*L) : nullptr;
+    if (u8 && !T) return 0;
+    if (Lm == 0 || nq == 0) return 0;
+    BatchGuard bg(L);
+    Replica& R = *L->reps.front();
+    if (!HIP_CHECK(hipSetDevice(R.device))) return 0;
+    // 1. the queries as the device entry points take them: characters of cs bytes, byte offsets
+    DecodedStrings D;
+    if (u8) decode_strings(reinterpret_cast<const char* const*>(queries), nq, D);
+    auto chars_of = [&](uint32_t i, size_t& len) -> const void* {
+        if (u8) {
+            len = D.ptr[i] ? str_len(D.ptr[i]) : 0;
+            return D.ptr[i];
+        }
+        len = queries[i] ? str_len(queries[i]) : 0;
+        return queries[i];
+    };
+    const uint32_t chunk = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, kSimChunkRecords / Lm));
+    SimBuffers M;
+    uint64_t* d_off = nullptr;
+    uint32_t *d_n = nullptr, *d_k = nullptr;
+    float *d_s = nullptr, *d_v = nullptr;
+    const size_t recs = (size_t)chunk * Lm;
+    if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_off, (size_t)chunk + 1) ||
+        !M.alloc(&d_n, chunk) || !M.alloc(&d_k, recs) || !M.alloc(&d_s, recs) || !M.alloc(&d_v, recs))
+        return 0;
+    std::vector<uint32_t> cnt(nq, 0), keys, h_n(chunk), h_k(recs);  // (counts stay zero unless the whole call succeeds)
+    std::vector<float> sc, sv, h_s(recs), h_v(recs);
+    std::vector<uint64_t> h_off((size_t)chunk + 1);
+    std::vector<uint8_t> h_raw;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t B = std::min(chunk, nq - q0);
+        h_raw.clear();
+        h_off[0] = 0;
+        for (uint32_t i = 0; i < B; ++i) {
+            size_t len = 0;
+            const uint8_t* p = static_cast<const uint8_t*>(chars_of(q0 + i, len));
+            if (len) h_raw.insert(h_raw.end(), p, p + len * cs);
+            h_off[i + 1] = h_raw.size();
+        }
+        uint8_t* d_raw = nullptr;
+        if (!M.alloc(&d_raw, h_raw.size() + 8)) return 0;
+        if (!HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, M.stream)) ||
+            (!h_raw.empty() &&
+             !HIP_CHECK(hipMemcpyAsync(d_raw, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, M.stream))))
+            return 0;
+        // 2. the search, 3. the re-rank behind it
+        if (search_on_replica(*L, R, d_raw, d_off, B, thr, Lm, Lm, d_n, d_k, d_s, M.stream) != 0) {
+            if (!t_last_error) t_last_error = kErrInternal;
+            return 0;
+        }
+        if (queue_similarity(*L, R, d_raw, d_off, B, Lm, d_n, d_k, d_s, d_v, true, min_sim, M.stream) != 0) return 0;
+        // 4. everything back
+        const size_t rb = (size_t)B * Lm;
+        if (!HIP_CHECK(hipMemcpyAsync(h_n.data(), d_n, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_k.data(), d_k, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_s.data(), d_s, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_v.data(), d_v, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipStreamSynchronize(M.stream)))
+            return 0;
+        for (uint32_t i = 0; i < B; ++i) {
+            const uint32_t c = std::min(h_n[i], Lm);
+            const size_t at = (size_t)i * Lm;
+            cnt[q0 + i] = c;
+            keys.insert(keys.end(), h_k.begin() + at, h_k.begin() + at + c);
+            sc.insert(sc.end(), h_s.begin() + at, h_s.begin() + at + c);
+            sv.insert(sv.end(), h_v.begin() + at, h_v.begin() + at + c);
+        }
+    }
+    // 5. the result pointers, and the third flat array
+    std::copy(cnt.begin(), cnt.end(), counts);
+    const uint32_t total = marshal(*L, keys, sc, results, scores, T);
+    *sims = new float[std::max<size_t>(sv.size(), 1)];
+    std::copy(sv.begin(), sv.end(), *sims);
+    return total;
+}
 }  // namespace
 }  // namespace ngs
 
@@ -2659,37 +2877,8 @@ NGS_API int ngsSearchDevice(uint32_t handle, const uint8_t* dQueryBytes, const u
     Replica& R = *Rp;
     hipStream_t s = (hipStream_t)stream;
     BatchGuard bg(L);
-    if (Lm == 0) {
-        return HIP_CHECK(hipMemsetAsync(dCounts, 0, sizeof(uint32_t) * nQueries, s)) &&
-                       HIP_CHECK(hipStreamSynchronize(s))
-                   ? 0
-                   : -4;
-    }
-    std::unique_ptr<Context> c = R.acquire();
-    if (!c) return -4;
-    // The batch's byte count sizes the normalised-query buffer. A context that has one already
-    // launches without reading it back (a sync before any kernel); k_prep flags a batch that
-    // does not fit and the call reruns after the read-back.
-    int rc = 0;
-    auto read_bytes = [&](uint64_t& qb) -> bool {
-        return HIP_CHECK(hipMemcpyAsync(&qb, dQueryOffsets + nQueries, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) &&
-               HIP_CHECK(hipStreamSynchronize(s));
-    };
-    uint64_t qbytes = 0;
-    if (nQueries && !c->qcap && !read_bytes(qbytes)) rc = -4;
-    if (!rc) rc = device_search(*L, R, *c, dQueryBytes, dQueryOffsets, nQueries, qbytes, threshold, Lm, outStride,
-                                dCounts, dKeys, dScores, s);
-    if (rc == kRetryQcap) {
-        rc = read_bytes(qbytes) ? device_search(*L, R, *c, dQueryBytes, dQueryOffsets, nQueries, qbytes, threshold, Lm,
-                                                outStride, dCounts, dKeys, dScores, s)
-                                : -4;
-        if (rc == kRetryQcap) {
-            rc = -5;
-            t_last_error = kErrQueryBuffer;
-        }
-    }
-    R.give_back(std::move(c));
-    return rc;
+    return search_on_replica(*L, R, dQueryBytes, dQueryOffsets, nQueries, threshold, Lm, outStride, dCounts, dKeys,
+                             dScores, s);
 }
 
 // Asynchronous form (bench.py's pipeline; a server's batches): queue the search on a pooled
@@ -2847,6 +3036,52 @@ NGS_API int ngsPackResults(const uint32_t* dCounts, const uint32_t* dKeys, const
                                        (hipStream_t)stream))
                ? 0
                : -4;
+}
+
+NGS_API int ngsSimilarityDevice(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                uint32_t nQueries, uint32_t stride, const uint32_t* dCounts, const uint32_t* dKeys,
+                                float* dSim, void* stream) {
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim)) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = sim_entry(handle, L, R)) return rc;
+    BatchGuard bg(L);
+    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
+                            const_cast<uint32_t*>(dKeys), nullptr, dSim, false, 0.0f, (hipStream_t)stream);
+}
+
+NGS_API int ngsRerankDevice(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                            uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
+                            float* dSim, float minSimilarity, void* stream) {
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
+        stride > kRerankMaxStride || minSimilarity != minSimilarity)
+        return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = sim_entry(handle, L, R)) return rc;
+    BatchGuard bg(L);
+    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, true,
+                            minSimilarity, (hipStream_t)stream);
+}
+
+NGS_API uint32_t scoreBatchSim(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                               uint32_t limit, float minSimilarity, uint32_t* counts, char*** results, float** scores,
+                               float** sims) {
+    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false);
+}
+
+NGS_API uint32_t scoreBatchSimW(uint32_t handle, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                uint32_t limit, float minSimilarity, uint32_t* counts, wchar_t*** results,
+                                float** scores, float** sims) {
+    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false);
+}
+
+NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                                 uint32_t limit, float minSimilarity, uint32_t* counts, char*** results, float** scores,
+                                 float** sims) {
+    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, true);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

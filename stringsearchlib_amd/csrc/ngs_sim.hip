@@ -1,0 +1,453 @@
+// ngs_sim.hip — the verification stage behind the search: the edit-distance
+// similarity of every (query, key) record of a result block, and the re-rank by it, for gfx950.
+//
+// k_sim: one wave per query. The wave normalises the query as k_prep does (ballot windows find
+// the trim), then takes one of two wave-uniform paths by the normalised length m:
+//   m <= 64   lanes are records: the query's match masks go to LDS once, and every lane follows
+//             key -> term -> term_off -> term_bytes and streams its term through the one-word global
+//             Myers recurrence (ngs_sim.h: myers_step with hin = +1);
+//   m <= 4096 one record at a time, the wave as a systolic pipeline: lane w holds query word w
+//             (its 64 characters in registers) and takes the horizontal delta lane w - 1 produced
+//             one step earlier.
+// k_rerank: one workgroup per query sorts (sim desc, position asc) in LDS and permutes in place.
+#include <hip/hip_runtime.h>
+
+#include "ngs_common.h"
+#include "ngs_sim.h"
+
+namespace ngs {
+namespace {
+
+struct SimArgs {
+    const uint8_t* raw;
+    const uint64_t* off;
+    const uint32_t* counts;
+    const uint32_t* keys;
+    float* sim;
+    const uint32_t* key_term;  // indexes without kt_off: the term of each key
+    uint32_t n, stride;
+    ValidSet V;
+};
+
+__device__ __forceinline__ uint32_t ld_char(const uint8_t* base, uint64_t i, uint32_t cs) {
+    return cs == 4 ? reinterpret_cast<const uint32_t*>(base)[i] : (uint32_t)base[i];
+}
+
+// the terms of key `key`: [j, je) of kt_term, or the one term of key_term (j = 0, je = 1)
+__device__ __forceinline__ void key_terms(const DevIndex& X, uint32_t key, uint32_t& j, uint32_t& je) {
+    if (X.kt_off) {
+        j = X.kt_off[key];
+        je = X.kt_off[key + 1];
+    } else {
+        j = 0;
+        je = 1;
+    }
+}
+__device__ __forceinline__ uint32_t term_at(const DevIndex& X, const uint32_t* key_term, uint32_t key, uint32_t j) {
+    return X.kt_off ? X.kt_term[j] : key_term[key];
+}
+
+// d(Q, T) of a narrow term through the byte-indexed mask table: the term is read a dword at a
+// time with the next one in flight, as myers_match_t does (term_bytes is padded by two dwords)
+__device__ __forceinline__ uint32_t myers_narrow(const uint64_t* peq, uint32_t m, const uint8_t* tb, uint64_t a,
+                                                 uint32_t L) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(tb + (a & ~(uint64_t)3));
+    const uint32_t skip = (uint32_t)(a & 3u);
+    uint32_t cur = w[0] >> (8u * skip), nxt = skip + L > 4u ? w[1] : 0u;
+    uint32_t avail = 4u - skip, k = 1, score = m;
+    const uint64_t top = 1ull << (m - 1u);
+    MyersBlock b;
+    for (uint32_t j = 0; j < L; ++j) {
+        if (!avail) {
+            cur = nxt;
+            avail = 4u;
+            ++k;
+            if (j + 4u < L) nxt = w[k];
+        }
+        const uint32_t c = cur & 255u;
+        cur >>= 8;
+        --avail;
+        score += (uint32_t)myers_step(b, peq[c], +1, top);
+    }
+    return score;
+}
+
+// the wide table: kSimSlots masks, then kSimSlots keys; a character not in it matches no row
+__device__ __forceinline__ uint64_t wide_mask(const uint64_t* mask, const uint32_t* slot_key, uint32_t c) {
+    uint32_t s = sim_slot(c);
+    for (;;) {
+        const uint32_t k = slot_key[s];
+        if (k == c) return mask[s];
+        if (k == kSimEmpty) return 0;
+        s = (s + 1u) & (kSimSlots - 1u);
+    }
+}
+__device__ __forceinline__ uint32_t myers_wide(const uint64_t* mask, const uint32_t* slot_key, uint32_t m,
+                                               const uint32_t* t, uint32_t L) {
+    const uint64_t top = 1ull << (m - 1u);
+    MyersBlock b;
+    uint32_t score = m, nxt = t[0];
+    for (uint32_t j = 0; j < L; ++j) {
+        const uint32_t c = nxt;
+        if (j + 1u < L) nxt = t[j + 1u];
+        score += (uint32_t)myers_step(b, wide_mask(mask, slot_key, c), +1, top);
+    }
+    return score;
+}
+
+template <bool kWide>
+__global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
+    constexpr uint32_t cs = kWide ? 4u : 1u;
+    __shared__ uint64_t s_mask[256];             // narrow: by byte; wide: slots [0, kSimSlots)
+    __shared__ uint32_t s_key[kSimSlots];        // wide: the slots' characters
+    __shared__ uint32_t s_valid[8];
+    const uint32_t lane = threadIdx.x, q = blockIdx.x;
+    if (lane < 8) s_valid[lane] = A.V.w[lane];
+    __syncthreads();  // (the workgroup is one wave: the barriers here order its LDS accesses only)
+
+    const uint32_t count = min(A.counts[q], A.stride);
+    if (count == 0) return;
+    const uint32_t* keys = A.keys + (size_t)q * A.stride;
+    float* out = A.sim + (size_t)q * A.stride;
+    const uint64_t qa = A.off[q], qe = A.off[q + 1];
+    const uint64_t n = qe > qa ? (qe - qa) / cs : 0;
+    const uint8_t* rq = A.raw + qa;
+
+    // wildcard, trim, length: everything here is uniform over the wave
+    float fixed = 0.0f;
+    bool is_fixed = false;
+    uint64_t first = n, m64 = 0;
+    if (n == 0 || (n == 1 && ld_char(rq, 0, cs) == (uint32_t)'*')) {
+        fixed = kSimWildcard;
+        is_fixed = true;
+    } else {
+        for (uint64_t base = 0; base < n; base += 64) {
+            const uint64_t i = base + lane;
+            const uint64_t bal = __ballot(i < n && sim_keeps(s_valid, ld_char(rq, i, cs), cs));
+            if (bal) {
+                first = base + (uint32_t)__ffsll((unsigned long long)bal) - 1u;
+                break;
+            }
+        }
+        if (first < n) {
+            uint64_t last = first;
+            for (uint64_t base = 0; base < n; base += 64) {
+                const uint64_t i = base + lane;
+                const uint64_t bal = __ballot(i < n && sim_keeps(s_valid, ld_char(rq, n - 1 - i, cs), cs));
+                if (bal) {
+                    last = n - 1 - (base + (uint32_t)__ffsll((unsigned long long)bal) - 1u);
+                    break;
+                }
+            }
+            m64 = last - first + 1;
+        }
+        if (m64 > kSimMaxQuery) {
+            fixed = kSimNone;
+            is_fixed = true;
+        }
+    }
+    if (is_fixed) {
+        for (uint32_t r = lane; r < count; r += 64) out[r] = fixed;
+        return;
+    }
+    const uint32_t m = (uint32_t)m64;
+    const uint8_t* nq = rq + first * cs;  // Q[i] = sim_norm(nq[i])
+
+    if (m <= 64) {
+        // ---- short path: match masks in LDS, lanes are records ----
+        const uint32_t qc = lane < m ? sim_norm(s_valid, ld_char(nq, lane, cs), cs) : kSimEmpty;
+        uint64_t mine = 0;  // the rows holding this lane's character
+        for (uint32_t i = 0; i < m; ++i) mine |= __shfl(qc, (int)i) == qc ? 1ull << i : 0ull;
+        if (kWide) {
+            s_key[lane] = kSimEmpty;
+            s_key[lane + 64] = kSimEmpty;
+        } else {
+            for (uint32_t i = lane; i < 256; i += 64) s_mask[i] = 0;
+        }
+        __syncthreads();
+        if (lane < m) {
+            if (!kWide) {
+                s_mask[qc] = mine;  // (lanes of one character store one value)
+            } else if ((uint32_t)__ffsll((unsigned long long)mine) - 1u == lane) {  // a character's first row inserts it
+                uint32_t s = sim_slot(qc);
+                for (;;) {
+                    const uint32_t old = atomicCAS(&s_key[s], kSimEmpty, qc);
+                    if (old == kSimEmpty || old == qc) break;
+                    s = (s + 1u) & (kSimSlots - 1u);
+                }
+                s_mask[s] = mine;
+            }
+        }
+        __syncthreads();
+
+        // rounds of 64 records; the next round's key -> term -> offsets chain is issued before
+        // the current round's recurrence
+        uint32_t key = lane < count ? keys[lane] : kSimEmpty;
+        uint32_t j = 0, je = 0;
+        uint64_t ta = 0, tb = 0;
+        auto first_term = [&](uint32_t k, uint32_t& fj, uint32_t& fje, uint64_t& fa, uint64_t& fb) {
+            fj = fje = 0;
+            fa = fb = 0;
+            if (k >= X.n_keys) return;
+            key_terms(X, k, fj, fje);
+            if (fj >= fje) return;
+            const uint32_t t = term_at(X, A.key_term, k, fj);
+            if (t >= X.n_terms) return;
+            fa = X.term_off[t];
+            fb = X.term_off[t + 1];
+        };
+        first_term(key, j, je, ta, tb);
+        for (uint32_t base = 0; base < count; base += 64) {
+            const uint32_t r = base + lane, rn = r + 64;
+            const uint32_t nkey = rn < count ? keys[rn] : kSimEmpty;
+            uint32_t nj, nje;
+            uint64_t na, nb;
+            first_term(nkey, nj, nje, na, nb);
+            float best = kSimNone;
+            while (j < je) {
+                if (tb > ta) {
+                    const uint32_t L = (uint32_t)(tb - ta);
+                    uint32_t d = L;  // an empty Q: L insertions
+                    if (m) {
+                        if (kWide) d = myers_wide(s_mask, s_key, m, reinterpret_cast<const uint32_t*>(X.term_bytes) + ta, L);
+                        else d = myers_narrow(s_mask, m, X.term_bytes, ta, L);
+                    }
+                    best = fmaxf(best, sim_value(d, m, L));
+                }
+                if (++j < je) {
+                    const uint32_t t = term_at(X, A.key_term, key, j);
+                    ta = tb = 0;
+                    if (t < X.n_terms) {
+                        ta = X.term_off[t];
+                        tb = X.term_off[t + 1];
+                    }
+                }
+            }
+            if (r < count) out[r] = best;
+            key = nkey;
+            j = nj;
+            je = nje;
+            ta = na;
+            tb = nb;
+        }
+        return;
+    }
+
+    // ---- long path: the wave is a systolic pipeline over the query's W words ----
+    const uint32_t W = (m + 63u) / 64u;
+    const uint32_t rows = lane + 1u < W ? 64u : (lane < W ? m - 64u * lane : 0u);
+    const uint64_t top = rows ? 1ull << (rows - 1u) : 0ull;
+    const uint64_t rowmask = rows == 64u ? ~0ull : (1ull << rows) - 1ull;
+    // this lane's 64 query characters: bytes packed four to a register, or one register each
+    constexpr uint32_t kRegs = kWide ? 64u : 16u;
+    uint32_t qw[kRegs];
+#pragma unroll
+    for (uint32_t i = 0; i < kRegs; ++i) qw[i] = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 64; ++i) {
+        const uint32_t c = i < rows ? sim_norm(s_valid, ld_char(nq, 64u * lane + i, cs), cs) : 0u;
+        if (kWide) qw[i] = c;
+        else qw[i >> 2] |= c << (8u * (i & 3u));
+    }
+    for (uint32_t r = 0; r < count; ++r) {
+        const uint32_t key = keys[r];
+        float best = kSimNone;
+        uint32_t j = 0, je = 0;
+        if (key < X.n_keys) key_terms(X, key, j, je);
+        for (; j < je; ++j) {
+            const uint32_t t = term_at(X, A.key_term, key, j);
+            if (t >= X.n_terms) continue;
+            const uint64_t ta = X.term_off[t];
+            const uint32_t L = (uint32_t)(X.term_off[t + 1] - ta);
+            if (!L) continue;
+            MyersBlock b;
+            uint32_t score = m;  // followed by lane W - 1
+            int hout = 0;
+            const uint32_t steps = L + W - 1u;
+            for (uint32_t s = 0; s < steps; ++s) {
+                // lane w is at term character s - w, with the delta lane w - 1 left at it one step ago
+                const int up = __shfl_up(hout, 1);
+                const int hin = lane == 0 ? +1 : up;
+                const uint32_t at = s - lane;
+                if (lane < W && at < L) {  // (s < lane wraps past L)
+                    const uint32_t c = ld_char(X.term_bytes, ta + at, cs);
+                    uint64_t eq = 0;
+#pragma unroll
+                    for (uint32_t i = 0; i < 64; ++i) {
+                        const uint32_t qi = kWide ? qw[i] : (qw[i >> 2] >> (8u * (i & 3u))) & 255u;
+                        eq |= qi == c ? 1ull << i : 0ull;
+                    }
+                    hout = myers_step(b, eq & rowmask, hin, top);
+                    if (lane == W - 1u) score += (uint32_t)hout;
+                }
+            }
+            const uint32_t d = (uint32_t)__shfl((int)score, (int)(W - 1u));
+            best = fmaxf(best, sim_value(d, m, L));
+        }
+        if (lane == 0) out[r] = best;
+    }
+}
+
+// ---- re-rank ----
+// One workgroup per query. Its size and its LDS follow the stride (launch_rerank): the sort runs over
+// n2 = the count rounded up to a power of two, n2 / 2 threads (64 .. kRerankThreads) make one
+// compare-exchange each per stage, and the sort keys take 8 bytes x the stride rounded up. At the
+// usual limit of 100 that is one wave and 1 KiB: with a fixed 256 threads and 32 KiB, 4,096 queries of
+// 100 records took 0.17 ms more.
+constexpr uint32_t kRerankThreads = 256;
+constexpr uint32_t kRerankPer = kRerankMaxStride / kRerankThreads;  // records a thread moves, at the most
+constexpr uint32_t kRerankMinSort = 128;  // counts up to 64 take the one-wave path
+__host__ __device__ inline uint32_t rerank_pow2(uint32_t n) {
+    uint32_t p = kRerankMinSort;
+    while (p < n) p <<= 1;
+    return p;
+}
+
+__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, mask);
+    const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), mask);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint32_t* __restrict__ counts,
+                                                            uint32_t* keys, float* scores, float* sim, float min_sim) {
+    extern __shared__ uint64_t s_rec[];  // rerank_pow2(stride) sort keys
+    __shared__ uint32_t s_kept;
+    const uint32_t tid = threadIdx.x, q = blockIdx.x, nthreads = blockDim.x;
+    const uint32_t count = min(counts[q], stride);
+    uint32_t* k = keys + (size_t)q * stride;
+    float* sc = scores + (size_t)q * stride;
+    float* sv = sim + (size_t)q * stride;
+    if (count <= 64) {
+        // one wave, no barrier: every lane holds its record, the sort runs through shuffles, and
+        // a lane fetches the record of its new position from the lane that loaded it
+        if (tid >= 64) return;
+        const bool live = tid < count;
+        const uint32_t rk = live ? k[tid] : 0u;
+        const float rs = live ? sc[tid] : 0.0f, rv = live ? sv[tid] : 0.0f;
+        uint64_t rec = live && !(rv < min_sim) ? rerank_key(__float_as_uint(rv), tid) : kRerankDropped;
+        for (uint32_t k2 = 2; k2 <= 64; k2 <<= 1)
+            for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+                const uint64_t other = shfl_xor64(rec, (int)j);
+                const bool keep_min = ((tid & k2) == 0) == ((tid & j) == 0);
+                rec = keep_min ? (rec < other ? rec : other) : (rec > other ? rec : other);
+            }
+        const uint32_t kept = (uint32_t)__popcll(__ballot(rec != kRerankDropped));
+        const int src = (int)((uint32_t)rec & 63u);
+        const uint32_t ok = (uint32_t)__shfl((int)rk, src);
+        const float os = __shfl(rs, src), ov = __shfl(rv, src);
+        if (tid < kept) {
+            k[tid] = ok;
+            sc[tid] = os;
+            sv[tid] = ov;
+        }
+        if (tid == 0) counts[q] = kept;
+        return;
+    }
+    const uint32_t n2 = rerank_pow2(count);
+    if (tid == 0) s_kept = 0;
+    for (uint32_t i = tid; i < n2; i += nthreads) {
+        uint64_t rec = kRerankDropped;
+        if (i < count) {
+            const float v = sv[i];
+            if (!(v < min_sim)) rec = rerank_key(__float_as_uint(v), i);
+        }
+        s_rec[i] = rec;
+    }
+    __syncthreads();
+    for (uint32_t k2 = 2; k2 <= n2; k2 <<= 1)
+        for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
+            for (uint32_t i = tid; i < n2; i += nthreads) {
+                const uint32_t p = i ^ j;
+                if (p > i) {
+                    const uint64_t a = s_rec[i], b = s_rec[p];
+                    if ((a > b) == ((i & k2) == 0)) {
+                        s_rec[i] = b;
+                        s_rec[p] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    // the kept records are a prefix: its last entry reports the new count
+    for (uint32_t i = tid; i < n2; i += nthreads)
+        if (s_rec[i] != kRerankDropped && (i + 1 == n2 || s_rec[i + 1] == kRerankDropped)) s_kept = i + 1;
+    __syncthreads();
+    const uint32_t kept = s_kept;
+    // in place: every record is read into registers before any is written
+    uint32_t mk[kRerankPer];
+    float ms[kRerankPer], mv[kRerankPer];
+#pragma unroll
+    for (uint32_t u = 0; u < kRerankPer; ++u) {
+        const uint32_t i = tid + u * nthreads;
+        mk[u] = 0;
+        ms[u] = mv[u] = 0.0f;
+        if (i < kept) {
+            const uint32_t p = (uint32_t)s_rec[i];
+            mk[u] = k[p];
+            ms[u] = sc[p];
+            mv[u] = sv[p];
+        }
+    }
+    // the loads of every wave have returned (s_waitcnt 0: this wave's outstanding memory operations
+    // are complete; the barrier joins the waves) before any wave stores over them. A device-scope
+    // fence here also wrote back and invalidated caches per workgroup: 0.10 ms per 4,096 queries.
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+#pragma unroll
+    for (uint32_t u = 0; u < kRerankPer; ++u) {
+        const uint32_t i = tid + u * nthreads;
+        if (i < kept) {
+            k[i] = mk[u];
+            sc[i] = ms[u];
+            sv[i] = mv[u];
+        }
+    }
+    if (tid == 0) counts[q] = kept;
+}
+
+// key_term[tk[p].x] = t for every pair p of term t (keys with one pair each: no two pairs write one key)
+__global__ __launch_bounds__(256) void k_key_term(DevIndex X, uint32_t* __restrict__ key_term) {
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= X.n_terms) return;
+    const uint32_t p = X.tk_identity ? t : X.tk_off[t], pe = X.tk_identity ? t + 1 : X.tk_off[t + 1];
+    for (uint32_t i = p; i < pe; ++i) {
+        const uint32_t key = X.tk[i].x;
+        if (key < X.n_keys) key_term[key] = t;
+    }
+}
+
+}  // namespace
+
+hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term, const uint8_t* raw,
+                             const uint64_t* off, uint32_t n, uint32_t stride, const uint32_t* counts,
+                             const uint32_t* keys, float* sim, hipStream_t s) {
+    if (!n || !stride) return hipSuccess;
+    if (!X.kt_off && !key_term) return hipErrorInvalidValue;
+    SimArgs A{raw, off, counts, keys, sim, key_term, n, stride, {}};
+    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
+    if (X.csize == 4) hipLaunchKernelGGL(k_sim<true>, dim3(n), dim3(64), 0, s, X, A);
+    else hipLaunchKernelGGL(k_sim<false>, dim3(n), dim3(64), 0, s, X, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_rerank(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
+                         float min_sim, hipStream_t s) {
+    if (!n) return hipSuccess;
+    if (stride > kRerankMaxStride) return hipErrorInvalidValue;
+    const uint32_t n2 = rerank_pow2(stride);  // every count's sort fits: counts are read as at most the stride
+    const uint32_t threads = n2 / 2 < 64 ? 64 : (n2 / 2 > kRerankThreads ? kRerankThreads : n2 / 2);
+    static_assert(kRerankPer * kRerankThreads == kRerankMaxStride, "a thread moves at most kRerankPer records");
+    hipLaunchKernelGGL(k_rerank, dim3(n), dim3(threads), sizeof(uint64_t) * n2, s, stride, counts, keys, scores, sim,
+                       min_sim);
+    return hipGetLastError();
+}
+
+hipError_t build_key_term(const DevIndex& X, uint32_t* key_term, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(key_term, 0xFF, sizeof(uint32_t) * (size_t)(X.n_keys ? X.n_keys : 1u), s);
+    if (e != hipSuccess || !X.n_terms) return e;
+    hipLaunchKernelGGL(k_key_term, dim3((X.n_terms + 255u) / 256u), dim3(256), 0, s, X, key_term);
+    return hipGetLastError();
+}
+
+}  // namespace ngs

@@ -23,6 +23,7 @@ def _b(s) -> bytes:
 # ngsLastError's codes that are not HIP errors (include/ngram_search.h)
 NGS_ERR_INTERNAL = 0x10001
 NGS_ERR_QUERY_BUFFER = 0x10002
+NGS_ERR_RERANK_LIMIT = 0x10003
 
 
 def _check(what: str) -> None:
@@ -33,6 +34,9 @@ def _check(what: str) -> None:
         raise RuntimeError(f"{what} failed: a kernel reported an internal error (see stderr)")
     if e == NGS_ERR_QUERY_BUFFER:
         raise RuntimeError(f"{what} failed: the batch outgrew the normalised-query buffer")
+    if e == NGS_ERR_RERANK_LIMIT:
+        raise ValueError(f"{what} failed: the effective limit (min(limit, keys)) is above 4,096, the most the "
+                         f"re-rank takes per query")
     if e:
         raise RuntimeError(f"{what} failed: HIP error {e} (see stderr)")
 
@@ -122,7 +126,8 @@ class StringIndex:
     _q = staticmethod(_b)
     _string = staticmethod(C.string_at)
     _RES = C.POINTER(C.POINTER(C.c_char))
-    _fn = {"search": "search", "score": "score", "release": "release", "scoreBatch": "scoreBatch", "key": "ngsKey"}
+    _fn = {"search": "search", "score": "score", "release": "release", "scoreBatch": "scoreBatch", "key": "ngsKey",
+           "scoreBatchSim": "scoreBatchSim"}
 
     def _queries(self, queries):
         return (C.c_char_p * max(1, len(queries)))(*[_b(q) for q in queries])
@@ -190,6 +195,34 @@ class StringIndex:
             getattr(L, f["release"])(self.handle, res, sc)
         return out
 
+    def score_batch_sim(self, queries, threshold: float = 0.0, limit: int = 100, min_similarity: float = 0.0):
+        """scoreBatchSim: score_batch re-ranked by the edit-distance similarity (include/ngram_search.h):
+        one list of (key, score, sim) per query, records with sim < min_similarity dropped, the rest in
+        order of (sim descending, the search's order ascending). min(limit, keys) must be at most 4,096."""
+        L, f = _native.lib(), self._fn
+        nq = len(queries)
+        qs = self._queries(queries)
+        counts = (C.c_uint32 * max(1, nq))()
+        res = self._RES()
+        sc = C.POINTER(C.c_float)()
+        sv = C.POINTER(C.c_float)()
+        L.ngsLastError(1)
+        total = getattr(L, f["scoreBatchSim"])(self.handle, qs, nq, threshold, limit, min_similarity, counts,
+                                               C.byref(res), C.byref(sc), C.byref(sv))
+        if not total:
+            _check(f["scoreBatchSim"])
+        out, o = [], 0
+        for i in range(nq):
+            c = counts[i]
+            out.append([(self._string(res[o + j]), sc[o + j], sv[o + j]) for j in range(c)])
+            o += c
+        assert o == total
+        if res:
+            getattr(L, f["release"])(self.handle, res, sc)
+        if sv:
+            getattr(L, f["release"])(self.handle, None, sv)
+        return out
+
     def dispose(self) -> None:
         if self.handle:
             _native.lib().dispose(self.handle)
@@ -246,6 +279,24 @@ class StringIndex:
             raise RuntimeError(f"ngsSearchDevice failed: {rc}")
 
 
+    def similarity_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
+                          d_sim: int, stream: int = 0) -> None:
+        """ngsSimilarityDevice on raw device pointers: d_sim[i * stride + r] = the edit-distance similarity of
+        query i and key d_keys[i * stride + r], r < d_counts[i]; queued on `stream`, nothing waits."""
+        rc = _native.lib().ngsSimilarityDevice(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_sim,
+                                               stream or None)
+        if rc:
+            raise RuntimeError(f"ngsSimilarityDevice failed: {rc}")
+
+    def rerank_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
+                      d_scores: int, d_sim: int, min_similarity: float = 0.0, stream: int = 0) -> None:
+        """ngsRerankDevice on raw device pointers: the similarity, then every query's records filtered by
+        min_similarity and ordered by (sim descending, position ascending), in place; queued on `stream`."""
+        rc = _native.lib().ngsRerankDevice(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores,
+                                           d_sim, min_similarity, stream or None)
+        if rc:
+            raise RuntimeError(f"ngsRerankDevice failed: {rc}")
+
     def search_device_async(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int,
                             out_stride: int, d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> int:
         """ngsSearchDeviceAsync: queues the search and returns its ticket (wait_device(ticket))."""
@@ -292,7 +343,7 @@ class WideStringIndex(StringIndex):
     _CS = 4
     _RES = C.POINTER(_U32P)
     _fn = {"search": "searchW", "score": "scoreW", "release": "releaseW", "scoreBatch": "scoreBatchW",
-           "key": "ngsKeyW"}
+           "key": "ngsKeyW", "scoreBatchSim": "scoreBatchSimW"}
 
     def __init__(self, words, row_size: int = 1, weights=None, device: int | None = None, gram_size: int = 2,
                  devices=None):
@@ -360,7 +411,7 @@ class Utf8StringIndex(WideStringIndex):
     _INDEX = "indexU8"
     _RES = C.POINTER(C.POINTER(C.c_char))
     _fn = {"search": "searchU8", "score": "scoreU8", "release": "release", "scoreBatch": "scoreBatchU8",
-           "key": "ngsKeyU8"}
+           "key": "ngsKeyU8", "scoreBatchSim": "scoreBatchSimU8"}
 
     @staticmethod
     def _words(words):

@@ -1,0 +1,138 @@
+#!/usr/bin/env python3
+"""The cost of the similarity / re-rank stage behind the search.
+
+A 200,000-row synthetic library (stringsearchlib_amd.synth, one key per row), 4,096 queries of 12
+bytes cut from its keys with one substitution, threshold 0.3, limit 100, one process, one stream.
+ngsSearchDevice alone and ngsSearchDevice with ngsRerankDevice queued behind it are timed
+alternately: host clock from before the call to the end of a stream synchronise, 10 warm-ups of
+each, the median of --reps calls with the 10th / 90th percentiles as the spread. The stage's own
+time comes from HIP events around ngsRerankDevice (and around ngsSimilarityDevice alone) on the
+same stream. Records and term characters are counted on the host from the search's answer.
+Prints one JSON line.
+
+    python tools/sim_probe.py [--rows 200000] [--queries 4096] [--reps 30]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402  (one HIP runtime per process: torch's first)
+
+import sim_ref  # noqa: E402
+import stringsearchlib_amd as ssl  # noqa: E402
+from stringsearchlib_amd import _native  # noqa: E402
+
+SECTOR = 64  # bytes a random access fetches at the least
+
+
+def pct(v, q):
+    s = sorted(v)
+    return s[min(len(s) - 1, int(q * len(s)))]
+
+
+def spread(v):
+    return {"median": round(statistics.median(v), 4), "p10": round(pct(v, 0.1), 4), "p90": round(pct(v, 0.9), 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=200000)
+    ap.add_argument("--queries", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--threshold", type=float, default=0.3)
+    ap.add_argument("--limit", type=int, default=100)
+    ap.add_argument("--min-similarity", type=float, default=0.0)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("sim_probe: no GPU")
+    words, weights, rng = ssl.synth.gen_corpus(a.rows, seed=42)
+    queries = ssl.synth.gen_queries(words, 1, a.queries, rng)
+    ix = ssl.StringIndex(words, 1, weights, device=0)
+    nq, stride = len(queries), min(a.limit, ix.num_keys())
+    dev = torch.device("cuda:0")
+    offs = np.cumsum([0] + [len(q) for q in queries], dtype=np.int64)
+    raw = torch.frombuffer(bytearray(b"".join(queries) + bytes(16)), dtype=torch.uint8).to(dev)
+    off = torch.from_numpy(offs).to(dev)
+    dn = torch.zeros(nq, dtype=torch.int32, device=dev)
+    dk = torch.zeros(nq * stride, dtype=torch.int32, device=dev)
+    ds = torch.zeros(nq * stride, dtype=torch.float32, device=dev)
+    dv = torch.zeros(nq * stride, dtype=torch.float32, device=dev)
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    args = (raw.data_ptr(), off.data_ptr(), nq)
+    outs = (dn.data_ptr(), dk.data_ptr(), ds.data_ptr())
+
+    def search():
+        t = time.perf_counter()
+        ix.search_device(*args, a.threshold, a.limit, stride, *outs, st.cuda_stream)
+        st.synchronize()
+        return (time.perf_counter() - t) * 1e3
+
+    def search_rerank():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t = time.perf_counter()
+        ix.search_device(*args, a.threshold, a.limit, stride, *outs, st.cuda_stream)
+        e0.record(st)
+        ix.rerank_device(*args, stride, *outs, dv.data_ptr(), a.min_similarity, st.cuda_stream)
+        e1.record(st)
+        st.synchronize()
+        return (time.perf_counter() - t) * 1e3, e0.elapsed_time(e1)
+
+    def similarity_alone():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        ix.similarity_device(*args, stride, dn.data_ptr(), dk.data_ptr(), dv.data_ptr(), st.cuda_stream)
+        e1.record(st)
+        st.synchronize()
+        return e0.elapsed_time(e1)
+
+    for _ in range(a.warmup):
+        search()
+        search_rerank()
+    t_search, t_both, t_stage, t_sim = [], [], [], []
+    for _ in range(a.reps):
+        t_search.append(search())
+        # the search's answer as the stage finds it: records, term characters, bytes its gathers touch
+        if not t_both:
+            counts = dn.cpu().numpy().astype(np.int64)
+            keys = dk.cpu().numpy().view(np.uint32).reshape(nq, stride)
+            klen = np.zeros(ix.num_keys(), dtype=np.int64)
+            used = np.unique(np.concatenate([keys[i, :counts[i]] for i in range(nq)]))
+            for k in used:
+                klen[k] = len(sim_ref.normalise(ix.key(int(k))))  # one key per row: its term is the key normalised
+            lens = np.concatenate([klen[keys[i, :counts[i]]] for i in range(nq)])
+            records, term_chars = int(counts.sum()), int(lens.sum())
+            # key id (streamed), then three dependent random reads (key -> term, its two offsets, its bytes)
+            gather_bytes = int(4 * records + 2 * SECTOR * records + (SECTOR * ((lens + 3 + SECTOR - 1) // SECTOR)).sum())
+            t_sim.extend(similarity_alone() for _ in range(a.reps))
+        both, stage = search_rerank()
+        t_both.append(both)
+        t_stage.append(stage)
+    kept = int(dn.cpu().numpy().astype(np.int64).sum())
+    m = [len(sim_ref.normalise(q)) for q in queries]
+    long_q = np.array([x > 64 for x in m])
+    ms, mb, mg, mv = (statistics.median(x) for x in (t_search, t_both, t_stage, t_sim))
+    print(json.dumps({
+        "rows": a.rows, "queries": nq, "threshold": a.threshold, "limit": a.limit, "min_similarity": a.min_similarity,
+        "reps": a.reps, "warmup": a.warmup,
+        "search_ms": spread(t_search), "search_rerank_ms": spread(t_both), "ratio": round(mb / ms, 4),
+        "rerank_stage_ms": spread(t_stage), "similarity_kernel_ms": spread(t_sim),
+        "records": records, "records_kept": kept, "term_chars": term_chars,
+        "records_per_s": round(records / (mg * 1e-3)), "term_chars_per_s": round(term_chars / (mg * 1e-3)),
+        "long_path_share": round(float(counts[long_q].sum()) / max(records, 1), 6),
+        "gather_bytes": gather_bytes, "gather_GBps_similarity": round(gather_bytes / (mv * 1e-3) / 1e9, 2),
+        "version": _native.lib().ngsVersion().decode()}))
+    ix.dispose()
+
+
+if __name__ == "__main__":
+    main()
