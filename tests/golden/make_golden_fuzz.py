@@ -18,7 +18,7 @@ import test_ref_fuzz as t  # noqa: E402
 
 def main():
     os.makedirs(t.RECORDED, exist_ok=True)
-    for name, spec in (("large_weights", t.LARGE_WEIGHTS), ("degenerate_args", t.DEGENERATE)):
+    for name, spec in t.SPECS.items():
         ref = t.RecordingReference()
         cases, ambiguous, failures = t.fuzz(ref, **spec)
         assert not failures, failures[0]

@@ -15,6 +15,16 @@ Cases whose reference answer depends on unordered_map iteration order beyond (sc
 ties — a promoted key with another pair above 100 in the same calcScore pass — are counted
 and skipped (ngo_search_amb decides; ngs_oracle.c header). The wildcard queries "" / "*",
 whose multi-pair keys take "the last pair in hash order" (hpp:356-369), are not drawn here.
+
+A third stream, HOSTILE (recorded as hostile_inputs), puts the inputs to the reference that the two
+above leave out: bytes >= 0x80 (outside validChar, so escapeBlank turns them into blanks, and the gram
+hash runs over signed chars, nGramSearch.h:147-150), punctuation and tabs, NULL alias words inside
+tiny rows, alias words that several rows share, libraries of one or two words, terms of 60-80 characters (58-78 grams), FLT_MAX and
+subnormal weights next to normal ones, and libraries with the single weight 200 or 200.00002 (either
+side of the library's rank-list rule). Weights of +-inf are NOT drawn, like NaN weights: a short-search
+score of 0 gives inf * 0 = NaN in calcScore (hpp:326; std::max keeps a NaN first argument), and a NaN
+score has no order in ScoreComparer, so the reference's answer to such a case is whatever its sort leaves. Queries that are
+"" or "*" or blank once normalised are not drawn either.
 """
 from __future__ import annotations
 
@@ -160,17 +170,29 @@ def _queries(rng: random.Random, words, keys, n):
     return out
 
 
-def fuzz(ref, seed, n_cases, n_queries, thresholds, limits):
-    """Puts the seeded cases to `ref` and to the oracle; (cases, order-dependent cases, failures)."""
+def stream(seed, n_cases, n_queries, thresholds, limits, corpus, queries):
+    """The case stream of a spec, one library at a time: (words, row, weights, keys, [(query, threshold)]).
+    The rng is drawn from in a fixed order (the library, its queries, then one threshold per query), so
+    every consumer of a spec (fuzz() here, the recorder, tests/test_gpu_ref_fuzz.py) sees the same cases
+    as the recorded answers; a case is one (query, threshold) at one of the spec's limits."""
     rng = random.Random(seed)
+    cases = 0
+    while cases < n_cases:
+        words, row, weights, keys = corpus(rng)
+        qt = [(q, rng.choice(thresholds)) for q in queries(rng, words, keys, n_queries)]
+        yield words, row, weights, keys, qt
+        cases += len(qt) * len(limits)
+
+
+def fuzz(ref, **spec):
+    """Puts the seeded cases to `ref` and to the oracle; (cases, order-dependent cases, failures)."""
+    limits = spec["limits"]
     cases = ambiguous = 0
     failures = []
-    while cases < n_cases:
-        words, row, weights, keys = _corpus(rng)
+    for words, row, weights, keys, qt in stream(**spec):
         ref.open(words, row, weights)
         oi = OracleIndex(words, row, weights)
-        for q in _queries(rng, words, keys, n_queries):
-            thr = rng.choice(thresholds)
+        for q, thr in qt:
             full = ref.full(q, thr, limits)
             for limit in limits:
                 cases += 1
@@ -192,7 +214,7 @@ def fuzz(ref, seed, n_cases, n_queries, thresholds, limits):
 
 
 LARGE_WEIGHTS = dict(seed=20261018, n_cases=6000, n_queries=12, thresholds=[0.0, 0.0, 0.3, 0.5],
-                     limits=[1, 3, 100, 0])
+                     limits=[1, 3, 100, 0], corpus=_corpus, queries=_queries)
 
 
 def test_oracle_vs_reference_large_weights():
@@ -211,12 +233,107 @@ def test_oracle_vs_reference_large_weights():
 DEGENERATE_THRESHOLDS = [-1.0, float("nan"), 1.0, 1.5, 0.999, 1.0 / 3.0, 2.0 / 3.0, 0.7]
 DEGENERATE_LIMITS = [1, 2**31, 2**32 - 1, 0]
 DEGENERATE = dict(seed=61018, n_cases=2000, n_queries=8, thresholds=DEGENERATE_THRESHOLDS,
-                  limits=DEGENERATE_LIMITS)
+                  limits=DEGENERATE_LIMITS, corpus=_corpus, queries=_queries)
 
 
 def test_oracle_vs_reference_degenerate_args():
     for ref in references("degenerate_args"):
         cases, ambiguous, failures = fuzz(ref, **DEGENERATE)
+        print(f"{type(ref).__name__}: {cases} cases, {ambiguous} order-dependent in the reference (skipped), "
+              f"{len(failures)} failures")
+        assert not failures, f"{len(failures)} of {cases} cases differ; first: {failures[0]}"
+        assert ambiguous < cases // 10
+
+
+# ---- the hostile stream: the inputs the two streams above leave out (module docstring) ----
+FLT_MAX = 3.4028234663852886e38
+HOSTILE_ALPHABETS = [b"ABCDE\xe9\xff\x80", b"ABCab \t.-_#", b"ABC"]
+# 1e-45 and 1e-38 are subnormal in fp32 (flushing them to zero would change bits); 200 and 200.00002
+# (fp32 0x43480001) sit either side of the library's rank-list rule w <= 200
+HOSTILE_WEIGHTS = [1.0, 100.0, 150.0, 0.0, -1.0, 0.5, FLT_MAX, 1e-45, 1e-38, 200.0, 200.00002]
+HOSTILE_ONE_WEIGHT = [1.0, 200.0, 200.00002, -1.0, 1e-45, 0.5, 2.5]
+_VALID = set(b".%$ @0123456789abcdefghijklmnopqrstuvwxyzABCDEFGHIJKLMNOPQRSTUVWXYZ")  # nGramSearch.h:307-313
+
+
+def _normal(w: bytes) -> bytes:
+    """escapeBlank, trim, toUpper (nGramSearch.h:30-98) under the default validChar: the term of a word."""
+    return bytes(c if c in _VALID else 32 for c in w).strip(b" \t\n\v\f\r").upper()
+
+
+def _hostile_word(rng: random.Random, alpha: bytes) -> bytes:
+    r = rng.random()
+    n = rng.randint(1, 5) if r < 0.2 else rng.randint(6, 12) if r < 0.9 else rng.randint(60, 80)
+    return bytes(rng.choice(alpha) for _ in range(n))
+
+
+def _hostile_corpus(rng: random.Random):
+    alpha = rng.choice(HOSTILE_ALPHABETS)
+    n_rows = rng.randint(1, 14)
+    words, weights, keys = [], [], []
+    if rng.random() < 0.2:
+        # a one-weight library of distinct terms, one per key: unique keys and one pair per term, so
+        # the weight alone decides whether the library takes rank lists
+        w1 = rng.choice(HOSTILE_ONE_WEIGHT)
+        seen = set()
+        for _ in range(n_rows):
+            w = _hostile_word(rng, alpha)
+            if _normal(w) in seen or not _normal(w):
+                continue
+            seen.add(_normal(w))
+            keys.append(w)
+        if not keys:
+            keys.append(b"ABCABCA")
+        return list(keys), 1, [w1] * len(keys), keys
+    row = rng.choice([1, 1, 2, 3])
+    for _ in range(n_rows):
+        for j in range(row):
+            if j == 0 and keys and rng.random() < 0.15:
+                w = rng.choice(keys)                      # a repeated key: more pairs for one key
+            elif j and rng.random() < 0.1:
+                w = None                                  # a NULL alias word (hpp:150-157 skips it)
+            elif j and rng.random() < 0.15:
+                w = rng.choice([x for x in words if x])   # an alias other rows have: a term of several keys
+            else:
+                w = _hostile_word(rng, alpha)
+            if j == 0:
+                keys.append(w)
+            words.append(w)
+            weights.append(rng.choice(HOSTILE_WEIGHTS))
+    return words, row, weights, keys
+
+
+def _hostile_queries(rng: random.Random, words, keys, n):
+    real = [w for w in words if w]
+    out = []
+    for _ in range(n):
+        r = rng.random()
+        src = rng.choice(keys)
+        if r < 0.4:
+            q = src                                        # an exact key: promotion
+        elif r < 0.5:
+            q = src.lower()
+        elif r < 0.8:
+            w = rng.choice(real)
+            a = rng.randrange(len(w))
+            q = w[a:a + rng.randint(1, 9)]                 # a piece: short and long searches
+        else:
+            w = bytearray(rng.choice(real))
+            w[rng.randrange(len(w))] = rng.choice(b"ABCXYZ\xe9 ")
+            q = bytes(w)
+        if not _normal(q) or q.strip() == b"*":            # the wildcard, or blank once normalised
+            q = b"A"
+        out.append(q)
+    return out
+
+
+HOSTILE = dict(seed=20261019, n_cases=4000, n_queries=12, thresholds=[0.0, 0.3, 0.5, 1.0], limits=[1, 3, 100, 0],
+               corpus=_hostile_corpus, queries=_hostile_queries)
+SPECS = {"large_weights": LARGE_WEIGHTS, "degenerate_args": DEGENERATE, "hostile_inputs": HOSTILE}
+
+
+def test_oracle_vs_reference_hostile_inputs():
+    for ref in references("hostile_inputs"):
+        cases, ambiguous, failures = fuzz(ref, **HOSTILE)
         print(f"{type(ref).__name__}: {cases} cases, {ambiguous} order-dependent in the reference (skipped), "
               f"{len(failures)} failures")
         assert not failures, f"{len(failures)} of {cases} cases differ; first: {failures[0]}"
