@@ -44,7 +44,7 @@ constexpr size_t kPartBudget = size_t(1) << 30;      // bytes of sliced tier-1b 
 constexpr uint32_t kSmallSlices = 32;                // ... or term-id slices per query (sliced k_wave)
 constexpr size_t kSmallQ = size_t(64) << 10;         // ... and if their offsets + bytes fit this many bytes
 // the latency path's one block, device and pinned host: statistics | results | queries
-constexpr size_t kSioStats = sizeof(DevStats) * (kStatSlots + 1);
+constexpr size_t kSioStats = sizeof(StatsBlock);
 constexpr size_t kSioBytes = kSioStats + kSmallBlock + kSmallQ;
 constexpr int kRetryQcap = -6;                       // finish_search: rerun with the batch's byte count
 constexpr uint32_t kCalmCalls = 16;                  // grown survivor slots unused this many calls: halved
@@ -316,9 +316,7 @@ struct Context {
     uint32_t* d_qm = nullptr;
     uint32_t* d_glist = nullptr;
     uint32_t* d_list2 = nullptr;
-    uint32_t* d_gcount = nullptr;  // [0] general-path count, [1] tier-2 count, [2] tier-1b hand-overs, [3] heavy,
-                                   // [4] hand-overs of the heavy list's lean launch, [5] full list,
-                                   // [6] k_prep: a query past the normalised-query buffer (qcap)
+    uint32_t* d_gcount = nullptr;  // the path counts behind d_stats' slots (PathCounts); not read
     uint32_t* d_fb = nullptr;      // queries tier 1a handed to tier 1b
     uint32_t* d_fb2 = nullptr;     // ... from the heavy list (side stream)
     uint32_t* d_heavy = nullptr;   // queries the prep kernel listed as heavy (cmin 2)
@@ -343,7 +341,7 @@ struct Context {
     uint32_t* d_pcnt = nullptr;    // ... and their counts
     size_t pcap = 0, pncap = 0;    // records d_prec holds, counts d_pcnt holds
     uint32_t* d_group = nullptr;
-    // kStatSlots slots, then one holding d_gcount (one memset, one read-back), then the
+    // a StatsBlock (the statistics slots and the path counts: one memset, one read-back), then the
     // 2 * kListSlots counter lines of k_prep's slot lists (d_lctr; same memset, not read back)
     DevStats* d_stats = nullptr;
     uint32_t* d_lctr = nullptr;
@@ -493,17 +491,16 @@ struct Replica {
             if (!HIP_CHECK(hipEventCreate(&e))) return nullptr;
         for (hipEvent_t& e : c->piece_ev)
             if (!HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming))) return nullptr;
-        if (!dev_alloc(&c->d_group, kGeneralMaxGroup) || !dev_alloc(&c->d_stats, kStatSlots + 1 + 2 * kListSlots) ||
+        if (!dev_alloc(&c->d_group, kGeneralMaxGroup) || !dev_alloc(&c->d_stats, sizeof(StatsBlock) / sizeof(DevStats) + 2 * kListSlots) ||
             !dev_alloc(&c->d_sio, kSioBytes) ||
             !HIP_CHECK(hipMemsetAsync(c->d_sio, 0, kSioStats, c->stream)) ||
             !HIP_CHECK(hipStreamSynchronize(c->stream)) ||
             !HIP_CHECK(hipHostMalloc((void**)&c->h_sio, kSioBytes, hipHostMallocDefault)) ||
-            !HIP_CHECK(hipHostMalloc((void**)&c->h_stats, sizeof(DevStats) * (kStatSlots + 1), hipHostMallocDefault)))
+            !HIP_CHECK(hipHostMalloc((void**)&c->h_stats, sizeof(StatsBlock), hipHostMallocDefault)))
             return nullptr;
-        c->d_gcount = reinterpret_cast<uint32_t*>(c->d_stats + kStatSlots);
-        c->d_lctr = reinterpret_cast<uint32_t*>(c->d_stats + kStatSlots + 1);
-        static_assert(sizeof(DevStats) == 16 * sizeof(uint32_t), "k_prep's counters are 16 words apart");
-        static_assert(sizeof(DevStats) >= 7 * sizeof(uint32_t), "the path counts fit one stats slot");
+        StatsBlock* const sb = reinterpret_cast<StatsBlock*>(c->d_stats);
+        c->d_gcount = &sb->paths.general;
+        c->d_lctr = reinterpret_cast<uint32_t*>(sb + 1);
         return c;
     }
     void give_back(std::unique_ptr<Context> c) {
@@ -540,7 +537,7 @@ struct Server {
 
     bool init(int dev) {
         device = dev;
-        const size_t nst = (size_t)kServeSlots * (kStatSlots + 1);
+        const size_t nst = (size_t)kServeSlots * (sizeof(StatsBlock) / sizeof(DevStats));  // a StatsBlock per slot
         if (!HIP_CHECK(hipSetDevice(dev)) || !HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) ||
             !HIP_CHECK(hipHostMalloc((void**)&h, sizeof(ServeBlock) * kServeSlots,
                                      hipHostMallocCoherent | hipHostMallocMapped)) ||
@@ -1176,7 +1173,7 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
     // small: the statistics go to the latency block (zeroed by k_prep, read back by the caller
     // together with the results)
     DevStats* sd = small ? reinterpret_cast<DevStats*>(c.d_sio) : c.d_stats;
-    uint32_t* gc = reinterpret_cast<uint32_t*>(sd + kStatSlots);
+    PathCounts* pc = &reinterpret_cast<StatsBlock*>(sd)->paths;
     std::memset(&P, 0, sizeof(P));  // (padding too: the bytes are a replay signature, Context::gsig)
     P.thr = thr;
     P.limit = limit;
@@ -1212,7 +1209,7 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
         P.at = c.ablocks ? c.d_at : nullptr;  // null: no arena this call (ensure_arena)
         P.ac = c.ablocks ? c.d_ac : nullptr;
         P.ablocks = c.ablocks;
-        P.actr = gc + kArenaCtrWord;
+        P.actr = &pc->arena_used;
     }
     constexpr uint32_t list_slices = kSlices;        // term-id slices of the hand-over / full lists' tier 1b
     constexpr uint32_t small_slices = kSmallSlices;  // ... and of every query of the latency path
@@ -1226,7 +1223,7 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
         P.nslices = ensure_parts(c, B, P.limit, list_slices);
     }
     P.qcap = c.qcap;
-    P.oflow = gc + 6;
+    P.oflow = &pc->oflow;
     if (small) {
         P.zero_stats = reinterpret_cast<uint32_t*>(sd);
         // the slots this batch's queries add to (q & (kStatSlots - 1), errors in slot 0); the
@@ -1311,7 +1308,7 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
     }
     // the call's operations, queued on s, or with gb appended to a graph being built (one-stream calls)
     auto queue_ops = [&](GraphBuild* gb) -> bool {
-        const size_t stat_bytes = sizeof(DevStats) * (kStatSlots + 1 + 2 * kListSlots);
+        const size_t stat_bytes = sizeof(StatsBlock) + sizeof(DevStats) * 2 * kListSlots;
         if (!zero_in_prep && !small) {
             if (gb) {
                 hipMemsetParams mp{};
@@ -1326,8 +1323,8 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
             }
         }
         if (timing) HIP_CHECK(hipEventRecord(c.ev[0], s));
-        if (!HIP_CHECK(launch_prep(d_raw, d_off, B, P, c.d_norm, c.d_qm, X.csize, X, c.d_heavy, gc + 3, c.d_full,
-                                   gc + 5, c.d_lslots, c.d_lctr, s, side, c.prep_ev, c.lists_ev, gb)))
+        if (!HIP_CHECK(launch_prep(d_raw, d_off, B, P, c.d_norm, c.d_qm, X.csize, X, c.d_heavy, &pc->heavy, c.d_full,
+                                   &pc->full, c.d_lslots, c.d_lctr, s, side, c.prep_ev, c.lists_ev, gb)))
             return false;
         if (timing) HIP_CHECK(hipEventRecord(c.ev[1], s));  // the end of k_prep is the start of the tier-1 phase
         // the main tier-1a launches of this replica's calls one after another: with two calls in flight
@@ -1344,9 +1341,10 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
             mwait = R.main_rec;
             R.main_rec = true;
         }
-        if (!HIP_CHECK(launch_fast(X, P, c.d_norm, d_off, c.d_qm, d_n, d_k, d_s, c.d_list2, gc + 1, c.d_fb, gc + 2,
-                                   c.d_fb2, gc + 4, c.d_heavy, gc + 3, c.d_full, gc + 5, c.d_glist, gc, sd, s, side,
-                                   side2, c.join, c.join2, c.lists_ev, all_heavy, mev, mwait, gb)))
+        if (!HIP_CHECK(launch_fast(X, P, c.d_norm, d_off, c.d_qm, d_n, d_k, d_s, c.d_list2, &pc->tier2, c.d_fb,
+                                   &pc->handover, c.d_fb2, &pc->heavy_handover, c.d_heavy, &pc->heavy, c.d_full, &pc->full,
+                                   c.d_glist, pc, sd, s, side, side2, c.join, c.join2, c.lists_ev, all_heavy, mev,
+                                   mwait, gb)))
             return false;
         if (timing) HIP_CHECK(hipEventRecord(c.ev[3], s));
         // the statistics and the path counts in one read-back (the general path adds no statistics)
@@ -1397,13 +1395,12 @@ int finish_search(Library& L, Replica& R, Context& c, uint32_t B, const SearchPa
     const bool timing = L.timing.load();
     ngs_stats st{};
     st.queries = B;
-    // general, tier 2, tier 1a hand-overs, heavy, heavy hand-overs, full
-    const uint32_t* counts3 = reinterpret_cast<const uint32_t*>(hst + kStatSlots);
-    if (counts3[6]) {  // (the rerun resets the path counts with the memset)
+    const PathCounts& pc = reinterpret_cast<const StatsBlock*>(hst)->paths;
+    if (pc.oflow) {  // (the rerun resets the path counts with the memset)
         c.stats_clean = false;
         return kRetryQcap;
     }  // a query past the normalised-query buffer: nothing is valid
-    const uint32_t ngen = counts3[0];
+    const uint32_t ngen = pc.general;
     if (ngen) {
         std::vector<uint32_t> gl(ngen);
         if (!HIP_CHECK(hipMemcpyAsync(gl.data(), c.d_glist, sizeof(uint32_t) * ngen, hipMemcpyDeviceToHost, s)) ||
@@ -1448,11 +1445,11 @@ int finish_search(Library& L, Replica& R, Context& c, uint32_t B, const SearchPa
     // count as slot_full): later calls get a larger arena, not more slots per query
     // (the queries it ran out for add the blocks they would still need, the next word: the next
     // call's arena is 5/4 of the estimated need, at least 3/2 of this one)
-    if (!small) c.heavy_items = counts3[3] * heavy_slices(P, counts3[3], R.dev);  // the next call's heavy grid
-    const uint32_t arena_used = small ? 0u : counts3[kArenaCtrWord];
+    if (!small) c.heavy_items = pc.heavy * heavy_slices(P, pc.heavy, R.dev);  // the next call's heavy grid
+    const uint32_t arena_used = small ? 0u : pc.arena_used;
     const bool arena_out = !small && P.at && arena_used > P.ablocks;
     if (arena_out) {
-        const uint64_t need = (uint64_t)P.ablocks + counts3[kArenaCtrWord + 1];
+        const uint64_t need = (uint64_t)P.ablocks + pc.arena_need;
         const uint64_t want = std::max<uint64_t>(3ull * P.ablocks / 2, 5ull * need / 4);
         const uint64_t cap = kArenaBudget / ((uint64_t)kArenaBlock * (sizeof(uint32_t) + sizeof(uint8_t)));
         c.arena_grow = (uint32_t)std::min<uint64_t>(want, cap);
@@ -1485,11 +1482,11 @@ int finish_search(Library& L, Replica& R, Context& c, uint32_t B, const SearchPa
         float ms = 0;
         st.fast_queries = ds.fast;
         st.general_queries = ngen;
-        st.tier2_queries = counts3[1];
+        st.tier2_queries = pc.tier2;
         // queries tier 1b ran: hand-overs of both lean launches and the full list
-        st.handover_queries = counts3[2] + counts3[4] + counts3[5];
-        st.heavy_queries = counts3[3];
-        st.full_queries = counts3[5];
+        st.handover_queries = pc.handover + pc.heavy_handover + pc.full;
+        st.heavy_queries = pc.heavy;
+        st.full_queries = pc.full;
         st.slot_full_queries = slot_full;
         st.survivor_slots = P.ecap;
         st.survivor_slot_bytes = ((uint64_t)c.ebcap * c.ecap + (uint64_t)c.ablocks * kArenaBlock) *
@@ -1655,8 +1652,8 @@ bool finish_host_chunk(Library& L, Replica& R, HostChunk& h, uint32_t Lm, std::v
     if (frc != 0) return false;
     ht.mark(kHpWait, "wait for kernels");
     if (h.small) {
-        const uint32_t* counts3 = reinterpret_cast<const uint32_t*>(c.h_sio) + kStatSlots * 16;
-        if (counts3[0]) {  // the general path ran after the read-back: read the results again
+        // the general path ran after the read-back: read the results again
+        if (reinterpret_cast<const StatsBlock*>(c.h_sio)->paths.general) {
             if (!HIP_CHECK(hipMemcpyAsync(c.h_sio + kSioStats, c.d_sio + kSioStats, h.block, hipMemcpyDeviceToHost,
                                           c.stream)) ||
                 !HIP_CHECK(hipStreamSynchronize(c.stream)))

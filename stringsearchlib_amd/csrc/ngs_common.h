@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 
 namespace ngs {
@@ -147,8 +148,6 @@ constexpr uint64_t kEmitWideBytes = 1ull << 30;       // ... halved until the ba
 constexpr uint32_t kEmitCapMax = 32768;              // ... grown up to this many per query
 constexpr uint32_t kArenaBlock = 1024;               // survivor arena block (entries; a multiple of 128)
 constexpr uint32_t kArenaChain = 128;                // blocks one query may chain (k_emit lists them in LDS)
-constexpr uint32_t kArenaCtrWord = 12;               // SearchParams.actr: this word of the path-count line
-                                                     // (and the next: blocks still needed when it ran out)
 constexpr uint64_t kEmitBudget = 16ull << 30;         // ... within this many bytes per context
 constexpr size_t kEmitWideBatch = 262144;             // tier 1a survivors per query spilled to HBM for k_emit
 constexpr uint32_t kWaveMaxGrams = 63;          // counts <= 63: one lane per count value
@@ -328,5 +327,41 @@ struct alignas(64) DevStats {  // accumulated by the fused kernel (one atomic pe
     unsigned long long main_postings;  // postings and lists of the queries the main tier-1a launch finished
     unsigned long long main_lists;     // (its own algorithmic bytes, bench.py's serialised roofline)
 };
+
+// The path counts of a call: one line behind the statistics slots, zeroed and read back with them.
+// The kernels take pointers to its words (the routing lists' counts, SearchParams.oflow / qhead / actr).
+struct alignas(64) PathCounts {
+    uint32_t general;         // queries listed for the general path (glist)
+    uint32_t tier2;           // ... for tier 2 (list2)
+    uint32_t handover;        // ... handed by tier 1a to tier 1b (fb)
+    uint32_t heavy;           // ... on the heavy list (cmin 2)
+    uint32_t heavy_handover;  // ... handed over by the heavy list's lean launch (fb2)
+    uint32_t full;            // ... on the full list (cmin 1, short search)
+    uint32_t oflow;           // k_prep: a query past the normalised-query buffer (SearchParams.oflow)
+    uint32_t pad0;
+    // item heads of the persistent tier-1b grids (SearchParams.qhead): the main launch's hand-overs,
+    // the heavy list's hand-overs, the full list
+    uint32_t head_main, head_heavy, head_full;
+    uint32_t pad1;
+    uint32_t arena_used;      // SearchParams.actr: survivor arena blocks taken
+    uint32_t arena_need;      // ... actr[1]: blocks still needed by the queries it ran out for
+    uint32_t pad2[2];
+};
+struct StatsBlock {
+    DevStats slot[kStatSlots];
+    PathCounts paths;
+};
+static_assert(sizeof(PathCounts) == sizeof(DevStats), "the path counts are one statistics slot");
+static_assert(sizeof(DevStats) == 16 * sizeof(uint32_t), "k_prep's list counters are 16 words apart");
+#define NGS_PATH_WORD(m) (offsetof(PathCounts, m) / sizeof(uint32_t))
+static_assert(NGS_PATH_WORD(general) == 0 && NGS_PATH_WORD(tier2) == 1 && NGS_PATH_WORD(handover) == 2 &&
+                  NGS_PATH_WORD(heavy) == 3 && NGS_PATH_WORD(heavy_handover) == 4 && NGS_PATH_WORD(full) == 5 &&
+                  NGS_PATH_WORD(oflow) == 6 /* k_prep zeroes the line's words but this one */ &&
+                  NGS_PATH_WORD(head_main) == 8 && NGS_PATH_WORD(head_heavy) == 9 && NGS_PATH_WORD(head_full) == 10 &&
+                  NGS_PATH_WORD(arena_used) == 12 && NGS_PATH_WORD(arena_need) == 13,
+              "the kernels and the host agree on these words");
+#undef NGS_PATH_WORD
+// (k_prep and k_serve address the line as slot kStatSlots of a DevStats array)
+static_assert(offsetof(StatsBlock, paths) == kStatSlots * sizeof(DevStats), "the line follows the slots");
 
 }  // namespace ngs

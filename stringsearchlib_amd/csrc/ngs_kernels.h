@@ -32,12 +32,13 @@ hipError_t launch_prep(const uint8_t* raw, const uint64_t* off, uint32_t B, cons
 // count in an LDS hash table per term-id part, threshold, term->key weighting, per-key max
 // merge and top-L in LDS. Queries it cannot take are appended to glist for the general path.
 // Tier 1 (k_wave, one wave per query: <= 64 grams, limit <= 128) then tier 2 (k_fast, one block
-// per query over list2: <= 255 grams, limit <= 1024); what remains goes to glist.
+// per query over list2: <= 255 grams, limit <= 1024); what remains goes to glist. paths: the call's
+// path counts (the general-path count, the tier-1b grids' item heads; the other counts' pointers).
 hipError_t launch_fast(const DevIndex& X, const SearchParams& P, const uint8_t* qnorm, const uint64_t* off,
                        const uint32_t* qm, uint32_t* out_n, uint32_t* out_k, float* out_s, uint32_t* list2,
                        uint32_t* count2, uint32_t* fb, uint32_t* fbc, uint32_t* fb2, uint32_t* fbc2,
                        const uint32_t* heavy, const uint32_t* hcount, const uint32_t* full,
-                       const uint32_t* fcount, uint32_t* glist, uint32_t* gcount, DevStats* stats, hipStream_t s,
+                       const uint32_t* fcount, uint32_t* glist, PathCounts* paths, DevStats* stats, hipStream_t s,
                        hipStream_t side, hipStream_t side2, hipEvent_t join, hipEvent_t join2,
                        hipEvent_t lists_ev, bool all_heavy = false, hipEvent_t main_ev = nullptr, bool main_wait = false,
                        GraphBuild* gb = nullptr);
@@ -45,7 +46,7 @@ hipError_t launch_fast(const DevIndex& X, const SearchParams& P, const uint8_t* 
 // The low-latency server (ngsServe): kServeSlots persistent one-wave workgroups on `s`, wave i
 // serving requests from blk[i] (coherent pinned host memory, device view) until blk[0].stop, or
 // until no request came to any slot for idle_ms (t_any: device memory, the latest request time),
-// or after life_ms in all. scratch: kServeSlots x (kStatSlots + 1) DevStats of device memory
+// or after life_ms in all. scratch: kServeSlots StatsBlocks of device memory, as DevStats
 // (statistics and the tier-2 routing count it ignores), list2: kServeSlots x 4 words.
 hipError_t launch_serve(const DevIndex& X, const SearchParams& P, ServeBlock* blk, DevStats* scratch,
                         uint32_t* list2, unsigned long long* t_any, uint32_t idle_ms, uint32_t life_ms, hipStream_t s);

@@ -3920,7 +3920,7 @@ hipError_t launch_fast(const DevIndex& X, const SearchParams& P, const uint8_t* 
                        const uint32_t* qm, uint32_t* out_n, uint32_t* out_k, float* out_s, uint32_t* list2,
                        uint32_t* count2, uint32_t* fb, uint32_t* fbc, uint32_t* fb2, uint32_t* fbc2,
                        const uint32_t* heavy, const uint32_t* hcount, const uint32_t* full,
-                       const uint32_t* fcount, uint32_t* glist, uint32_t* gcount, DevStats* stats, hipStream_t s,
+                       const uint32_t* fcount, uint32_t* glist, PathCounts* paths, DevStats* stats, hipStream_t s,
                        hipStream_t side, hipStream_t side2, hipEvent_t join, hipEvent_t join2,
                        hipEvent_t lists_ev, bool all_heavy, hipEvent_t main_ev, bool main_wait, GraphBuild* gb) {
     if (!P.n_queries) return hipSuccess;
@@ -3943,8 +3943,8 @@ hipError_t launch_fast(const DevIndex& X, const SearchParams& P, const uint8_t* 
             const uint32_t ghl = P.hgrid ? std::min(P.hgrid, ghb) : ghb;
             const uint32_t gfull = std::min<uint32_t>(P.n_queries, std::min<uint32_t>(persistent_slots(kWaveWavesPerSimd), kTier1bGrid));
             SearchParams PM = P, PHO = P;  // the main and the heavy hand-over launches
-            PM.qhead = gcount + 8;
-            PHO.qhead = gcount + 9;
+            PM.qhead = &paths->head_main;
+            PHO.qhead = &paths->head_heavy;
             // (esn[] was reset by k_prep)
             // main_ev (NGS_SERIAL_MAIN): the replica's last main launch, waited for (main_wait) before this
             // one and recorded after it, so that two calls in flight do not run their main launches at once
@@ -4018,7 +4018,7 @@ hipError_t launch_fast(const DevIndex& X, const SearchParams& P, const uint8_t* 
                 // measured 17 % slower than one wave (the hand-over lists below gain from slicing)
                 SearchParams PF = P;
                 PF.nslices = 1;
-                PF.qhead = gcount + 10;
+                PF.qhead = &paths->head_full;
                 klaunch(gb, k_wave, dim3(gfull), dim3(64), 0, side2, X, PF, qnorm, off, qm, out_n, out_k,
                                    out_s, list2, count2, stats, full, fcount);
                 dbg_check(side2, "k_wave (full list)");
@@ -4069,7 +4069,7 @@ hipError_t launch_fast(const DevIndex& X, const SearchParams& P, const uint8_t* 
     // blocks that mostly exit cost ~20 us at C2 and ~50 us at C3 per call)
     const uint32_t grid2 = std::min<uint32_t>(P.n_queries, P.limit > kWaveMaxLimit ? 1024u : 128u);
     klaunch(gb, k_fast, dim3(grid2), dim3(kFastThreads), 0, s, X, P, qnorm, off, qm, out_n, out_k, out_s,
-                       (const uint32_t*)list2, (const uint32_t*)count2, glist, gcount, stats);
+                       (const uint32_t*)list2, (const uint32_t*)count2, glist, &paths->general, stats);
     dbg_check(s, "k_fast");
     if (gb) return gb->err;
     return hipGetLastError();
