@@ -241,7 +241,11 @@ NGS_API int ngsServe(uint32_t handle, int enable);
  * i * stride) on `stream`: dOffsets[n + 1] = exclusive prefix sum of the counts (dOffsets[n] = total
  * records) and dRecords[2 * total] = {key id, fp32 score bits} per record in query order. Used by the
  * multi-GPU gather (stringsearchlib_amd/shard.py) so that the bytes sent to rank 0 follow the
- * results, not n x stride. Returns 0, -3 (bad argument), -4 (HIP error). */
+ * results, not n x stride. The block may come from anywhere: a count above `stride` is read as
+ * `stride`, by the prefix sum as by the copy (as ngsSimilarityDevice reads it), so dOffsets[n] is
+ * always the number of records written. The offsets are 32-bit: n x stride > 0xFFFFFFFF is refused
+ * with -3 before anything is queued or read. Returns 0, -3 (bad argument: NULL dCounts or dOffsets;
+ * with n > 0, stride 0 or NULL dKeys, dScores or dRecords; the overflow above), -4 (HIP error). */
 NGS_API int ngsPackResults(const uint32_t* dCounts, const uint32_t* dKeys, const float* dScores, uint32_t n,
                            uint32_t stride, uint32_t* dOffsets, uint32_t* dRecords, void* stream);
 

@@ -3012,6 +3012,7 @@ NGS_API int ngsServe(uint32_t handle, int enable) {
 NGS_API int ngsPackResults(const uint32_t* dCounts, const uint32_t* dKeys, const float* dScores, uint32_t n,
                            uint32_t stride, uint32_t* dOffsets, uint32_t* dRecords, void* stream) {
     if (!dCounts || !dOffsets || (n && (!dKeys || !dScores || !dRecords || !stride))) return -3;
+    if ((uint64_t)n * stride > 0xFFFFFFFFull) return -3;  // the offsets are 32-bit
     // the scan's scratch: one grow-only buffer per (device, stream), so that calls on different
     // streams never share one while their scans run; a buffer is replaced only after its stream's
     // earlier work has finished with it. (The mutex orders the host-side bookkeeping only.)

@@ -59,7 +59,8 @@ hipError_t launch_pack(const uint32_t* n, const uint32_t* k, const float* s, uin
                        uint32_t* pos, uint32_t* pk, float* ps, void* temp, size_t temp_bytes, hipStream_t st,
                        const uint64_t* koff = nullptr, uint64_t pbase = 0, uint32_t cs = 0, uint64_t* pp = nullptr);
 // ngsPackResults: counts[B] + records at i * stride -> pos[B + 1] (exclusive sum) and rec[2 * total]
-// = {key, score bits} pairs (the packed multi-GPU gather, stringsearchlib_amd/shard.py)
+// = {key, score bits} pairs (the packed multi-GPU gather, stringsearchlib_amd/shard.py); a count
+// above the stride counts as the stride in both
 size_t pack_pairs_temp_bytes(uint32_t B);
 hipError_t launch_pack_pairs(const uint32_t* n, const uint32_t* k, const float* s, uint32_t B, uint32_t stride,
                              uint32_t* pos, uint32_t* rec, void* temp, size_t temp_bytes, hipStream_t st);

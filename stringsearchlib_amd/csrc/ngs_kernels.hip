@@ -4083,7 +4083,9 @@ hipError_t launch_serve(const DevIndex& X, const SearchParams& P, ServeBlock* bl
 
 // one wave per query: its records to the packed arrays. With pp, each key goes out as the
 // caller's result pointer instead, pbase + key_off[key] * cs (the host image of the key bytes):
-// the random key_off gathers happen here, in HBM, not in the host's marshalling loop
+// the random key_off gathers happen here, in HBM, not in the host's marshalling loop.
+// (The host batches' packer: its counts come from the library's own kernels, which never write one
+// above the stride, so they are trusted here. ngsPackResults takes any block and clamps.)
 __global__ __launch_bounds__(256) void k_pack(const uint32_t* __restrict__ n, const uint32_t* __restrict__ k,
                                               const float* __restrict__ s, uint32_t B, uint32_t stride,
                                               const uint32_t* __restrict__ pos, uint32_t* __restrict__ pk,
@@ -4129,9 +4131,17 @@ __global__ __launch_bounds__(256) void k_pack_pairs(const uint32_t* __restrict__
     for (uint32_t i = lane; i < c; i += 64) rec[o + i] = make_uint2(k[src + i], __float_as_uint(s[src + i]));
 }
 
+// the caller's block may hold any count: one above the stride is read as the stride, by the scan
+// (through this input iterator, no extra pass) as by k_pack_pairs
+struct ClampCount {
+    uint32_t stride;
+    __host__ __device__ __forceinline__ uint32_t operator()(const uint32_t& c) const { return c < stride ? c : stride; }
+};
+using ClampedCounts = hipcub::TransformInputIterator<uint32_t, ClampCount, const uint32_t*>;
+
 size_t pack_pairs_temp_bytes(uint32_t B) {
     size_t bytes = 0;
-    hipcub::DeviceScan::InclusiveSum(nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+    hipcub::DeviceScan::InclusiveSum(nullptr, bytes, ClampedCounts(nullptr, ClampCount{0}), (uint32_t*)nullptr,
                                      (int)std::max<uint32_t>(B, 1));
     return bytes;
 }
@@ -4140,7 +4150,9 @@ size_t pack_pairs_temp_bytes(uint32_t B) {
 hipError_t launch_pack_pairs(const uint32_t* n, const uint32_t* k, const float* s, uint32_t B, uint32_t stride,
                              uint32_t* pos, uint32_t* rec, void* temp, size_t temp_bytes, hipStream_t st) {
     hipError_t e = hipMemsetAsync(pos, 0, sizeof(uint32_t), st);
-    if (e == hipSuccess && B) e = hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, n, pos + 1, (int)B, st);
+    if (e == hipSuccess && B)
+        e = hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, ClampedCounts(n, ClampCount{stride}), pos + 1, (int)B,
+                                             st);
     if (e != hipSuccess) return e;
     if (B) hipLaunchKernelGGL(k_pack_pairs, dim3((B + 3) / 4), dim3(256), 0, st, n, k, s, B, stride, pos,
                               reinterpret_cast<uint2*>(rec));

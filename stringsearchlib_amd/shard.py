@@ -129,8 +129,10 @@ def gather_to_root(counts, keys=None, scores=None, stride: int | None = None, gr
 
 def pack_torch(counts, keys, scores, n, stride, offsets, records):
     """ngsPackResults over torch tensors (CPU tests; the GPU path calls the library): offsets[n + 1]
-    = exclusive prefix sum of counts, records[2 * total] = {key, score bits} in query order."""
-    c = counts[:n].to(torch.int64)
+    = exclusive prefix sum of counts, records[2 * total] = {key, score bits} in query order. The
+    counts are the library's uint32 words (a negative int32 is a large one), and one above the
+    stride is read as the stride, by the sum as by the copy."""
+    c = (counts[:n].to(torch.int64) & 0xFFFFFFFF).clamp(max=stride)
     offsets[0] = 0
     offsets[1:n + 1] = torch.cumsum(c, 0).to(offsets.dtype)
     mask = torch.arange(stride, device=counts.device).unsqueeze(0) < c.view(n, 1)
@@ -180,13 +182,17 @@ class PackedGather:
         return 2 + pad_b + 2 * total
 
     @staticmethod
-    def decode(buf: torch.Tensor, pad_b: int):
-        """(counts, keys, scores) of a gathered packed buffer (its first words(pad_b, cap) words)."""
-        b, t = int(buf[0]), int(buf[1])
+    def decode(buf: torch.Tensor, pad_b: int, stride: int | None = None):
+        """(counts, keys, scores) of a gathered packed buffer (its first words(pad_b, cap) words).
+        With the sender's ``stride`` the counts are read as the packer read them (uint32 words, one
+        above the stride as the stride) and returned so."""
+        b, t = int(buf[0]), int(buf[1]) & 0xFFFFFFFF
         if not 0 <= b <= pad_b or buf.numel() < PackedGather.words(pad_b, t):
             raise ValueError(f"gathered buffer of batch {b}, {t} records in {buf.numel()} words does not match "
                              f"pad_b {pad_b}")
         counts = buf[2:2 + b]
+        if stride is not None:
+            counts = (counts.to(torch.int64) & 0xFFFFFFFF).clamp(max=stride).to(torch.int32)
         rec = buf[2 + pad_b:2 + pad_b + 2 * t].view(t, 2)
         if int(counts.sum()) != t:
             raise ValueError(f"gathered counts sum to {int(counts.sum())}, not the buffer's {t} records")
@@ -249,7 +255,7 @@ class PendingPacked:
         self.complete()
         if self.rank != 0:
             return None
-        return [PackedGather.decode(b, self.pg.pad_b) for b in self.bufs]
+        return [PackedGather.decode(b, self.pg.pad_b, self.pg.stride) for b in self.bufs]
 
 
 def gather_packed(pg: PackedGather, group=None, async_op: bool = False, cap: GatherCap | None = None):

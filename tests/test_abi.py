@@ -92,3 +92,26 @@ def test_wide_and_gram_size_entry_points_without_gpu_work():
     finally:
         L.disposeW(h)
     assert L.ngsCharSize(h) == 0
+
+
+def test_pack_results_refuses_bad_arguments_without_gpu_work():
+    """ngsPackResults checks its arguments before any HIP call, so integers stand in for the
+    device pointers and nothing is dereferenced: NULL counts or offsets; with n > 0 a stride of 0
+    or NULL keys, scores or records; and n x stride past the 32-bit offsets."""
+    L = _native.lib()
+    c, k, s, o, r = 0x1000, 0x2000, 0x3000, 0x4000, 0x5000
+    pack = L.ngsPackResults
+    assert pack(None, k, s, 4, 16, o, r, None) == -3
+    assert pack(c, k, s, 4, 16, None, r, None) == -3
+    assert pack(None, None, None, 0, 16, o, None, None) == -3  # n = 0 still needs the counts...
+    assert pack(c, None, None, 0, 16, None, None, None) == -3  # ...and the offsets
+    assert pack(c, k, s, 4, 0, o, r, None) == -3
+    assert pack(c, None, s, 4, 16, o, r, None) == -3
+    assert pack(c, k, None, 4, 16, o, r, None) == -3
+    assert pack(c, k, s, 4, 16, o, None, None) == -3
+    assert pack(c, k, s, 1, 0, o, r, None) == -3
+    # the offsets are uint32: n x stride must fit
+    for n, stride in ((0x10000, 0x10000), (0xFFFFFFFF, 2), (2, 0xFFFFFFFF), (0xFFFFFFFF, 0xFFFFFFFF),
+                      (0x80000000, 2), (65537, 65535 + 2)):
+        assert n * stride > 0xFFFFFFFF
+        assert pack(c, k, s, n, stride, o, r, None) == -3, (n, stride)

@@ -221,8 +221,10 @@ def test_general_select_limits(bench20k, kind):
     for thr, limit in [(0.0, 1), (0.0, 2), (0.3, 37), (0.5, 100), (0.0, 1024), (1.0, 1024), (0.3, 1025)]:
         st = _check(gi, oi, base, thr, limit, f"general-select-{kind}")
         assert st["general_queries"] == len(base), st
-    many = [w[:rng.randint(2, 3)] for w in rng.sample(live, 150)]
+    many = [w[:rng.randint(2, 3)] for w in rng.sample(live, 300)]  # past one group of 256
+    # (a group is min(256, 2 GiB / per-query state) queries: the budget does not cut it here)
+    assert (2 << 30) // (16 * (len(words) + gi.num_keys()) + 64) >= 256
     st = _check(gi, oi, many, 0.3, 100, f"general-groups-{kind}")
-    assert st["general_queries"] == len(many), st
+    assert st["general_queries"] == len(many) == 300, st
     if own:
         gi.dispose()

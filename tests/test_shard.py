@@ -123,3 +123,38 @@ def test_shard_bounds_cover_batch():
         spans = [shard.shard_bounds(r, world, 65536 + 5) for r in range(world)]
         assert spans[0][0] == 0 and spans[-1][1] == 65541
         assert all(a[1] == b[0] for a, b in zip(spans, spans[1:]))
+
+
+def test_pack_torch_reads_a_count_above_the_stride_as_the_stride():
+    """The CPU stand-in of ngsPackResults defines a count above the stride as the library does:
+    the prefix sum and the copy both read it as the stride (a negative int32 is a large uint32), so
+    the total is the number of records written, no record sits behind a hole, and decode accepts
+    the buffer with the clamped counts' sum."""
+    n, stride = 7, 4
+    raw = [2, stride + 1, 0, -2**31, 3, -1, stride]  # 2^31 and 0xFFFFFFFF as int32
+    clamped = [2, 4, 0, 4, 3, 4, 4]
+    pg = shard.PackedGather(n, stride, pad_b=9)
+    pg.counts.copy_(torch.tensor(raw, dtype=torch.int32))
+    pg.keys.copy_(torch.arange(100, 100 + n * stride, dtype=torch.int32))
+    pg.scores.copy_(torch.arange(n * stride, dtype=torch.float32) / 4)
+    pg.records.fill_(-7)
+    pg.pack()
+    total = sum(clamped)
+    assert pg.offsets.tolist() == [0, 2, 6, 6, 10, 13, 17, 21] and int(pg.buf[1]) == total
+    want_k = [100 + q * stride + i for q in range(n) for i in range(clamped[q])]
+    rec = pg.records[:2 * total].view(total, 2)
+    assert rec[:, 0].tolist() == want_k
+    assert rec[:, 1].contiguous().view(torch.float32).tolist() == [(k - 100) / 4 for k in want_k]
+    assert bool((pg.records[2 * total:] == -7).all())  # nothing written past the total
+    # the buffer still holds the block's counts as written: decode, told the stride, reads them as
+    # the packer did and accepts the buffer; without the stride their sum is not the total
+    assert pg.counts.tolist() == raw
+    c, k, s = shard.PackedGather.decode(pg.buf, 9, stride)
+    assert c.tolist() == clamped and k.tolist() == want_k
+    assert s.tolist() == [(x - 100) / 4 for x in want_k]
+    with pytest.raises(ValueError):
+        shard.PackedGather.decode(pg.buf, 9)
+    # ordinary counts decode alike with and without it
+    pg.counts.copy_(torch.tensor(clamped, dtype=torch.int32))
+    for got in (shard.PackedGather.decode(pg.pack().buf, 9), shard.PackedGather.decode(pg.buf, 9, stride)):
+        assert got[0].tolist() == clamped and got[1].tolist() == want_k
