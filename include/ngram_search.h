@@ -362,11 +362,14 @@ NGS_API int ngsLastStats(uint32_t handle, ngs_stats* out);
 /* Test support: digests of the index as the kernels read it, for comparing the GPU index build
  * (default) with the host build (environment NGS_HOST_GRAMS=1 / NGS_HOST_INTERN=1 at build time).
  * out[0..7] = postings, lists, skip buckets, FNV-1a of gram_off, post, gram_row, skip, bucket span
- * (zeros for dictionary indexes: gram sizes other than narrow 3); out[8..15] = FNV-1a of term_off,
+ * (gram_off has G + 1 and gram_row G entries: G = 2^21 gram codes for narrow gram size 3, the
+ * number of dictionary keys for every other index); out[8..15] = FNV-1a of term_off,
  * term_bytes, tk_off, tk, key_off, key_bytes, wildcard keys, wildcard scores; out[16] = shape flags
  * (1 keys unique, 2 one pair per term, 4 term ids in key-rank order, 8 rank lists: the threshold-0
- * shortcut of indexes with one weight, DevIndex.rank_post). Returns min(n, 17),
- * -1 (bad handle), -4 (HIP error). */
+ * shortcut of indexes with one weight, DevIndex.rank_post); out[17..19] = FNV-1a of the gram
+ * dictionary's lookup table as uploaded (ghash_key, ghash_val) and its size in bits (zeros for
+ * narrow gram size 3, which has no dictionary). Returns min(n, 20): a caller that passes 17 gets
+ * the first 17 words; -1 (bad handle), -4 (HIP error). */
 NGS_API int ngsIndexDigest(uint32_t handle, uint64_t* out, int n);
 /* The same digests of replica `replica` (0 .. ngsReplicaCount - 1): every replica of an index
  * placed on several devices holds the same arrays. -1 for a bad handle or replica. */

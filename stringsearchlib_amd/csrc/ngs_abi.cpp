@@ -415,6 +415,9 @@ struct Replica {
     int device = 0;
     DevIndex dev{};
     const float* wild_w = nullptr;  // the keys' wildcard weights (ngsSaveIndex reads them back)
+    // dictionary indexes: gram ids (rows of gram_off) and slots of ghash_key / ghash_val as uploaded
+    // (ngsReplicaDigest; the host's copies are freed after the upload)
+    uint64_t n_gram_ids = 0, ghash_slots = 0;
     std::vector<void*> owned;
     std::mutex pool_mu;
     std::vector<std::unique_ptr<Context>> pool;
@@ -741,6 +744,10 @@ bool upload_replica(Library& L, Replica& R, bool keys_unique, bool first) {
     uint32_t* ghash_val = nullptr;
     if (H.gram_mode == 1 && !(dev_upload(&ghash_key, H.ghash_key, R.owned) && dev_upload(&ghash_val, H.ghash_val, R.owned)))
         return false;
+    if (H.gram_mode == 1) {
+        R.n_gram_ids = H.gram_keys.size();
+        R.ghash_slots = H.ghash_key.size();
+    }
     X.gsz = H.gsz;
     X.csize = H.csize;
     X.gram_mode = H.gram_mode;
@@ -3137,10 +3144,10 @@ NGS_API int ngsReplicaDigest(uint32_t handle, int replica, uint64_t* out, int n)
         for (uint8_t c : v) h = (h ^ c) * 1099511628211ull;
         return true;
     };
-    uint64_t vals[16] = {};
-    if (X.gram_mode == 0) {  // the direct-indexed gram CSR (dictionary indexes: zeros)
+    uint64_t vals[20] = {};
+    {  // the gram CSR: direct-indexed (kGramSpace codes) or over the dictionary's gram ids
         uint64_t n_post = 0;
-        const size_t nspace = kGramSpace;
+        const size_t nspace = X.gram_mode == 0 ? (size_t)kGramSpace : (size_t)R.n_gram_ids;
         if (!HIP_CHECK(hipMemcpy(&n_post, X.gram_off + nspace, sizeof(uint64_t), hipMemcpyDeviceToHost))) return -4;
         const size_t rows = L.host.n_grams;
         const size_t sizes[4] = {sizeof(uint64_t) * (nspace + 1), sizeof(uint32_t) * n_post, sizeof(uint32_t) * nspace,
@@ -3170,8 +3177,16 @@ NGS_API int ngsReplicaDigest(uint32_t handle, int replica, uint64_t* out, int n)
     // the shape flags the kernels branch on
     const uint64_t flags = (X.keys_unique ? 1u : 0u) | (X.tk_identity ? 2u : 0u) | (X.tk_monotone ? 4u : 0u) |
                            (X.rank_post ? 8u : 0u);
-    const int m = std::min(n, 17);
-    for (int i = 0; i < m; ++i) out[i] = i < 16 ? vals[i] : flags;
+    vals[16] = flags;
+    // the gram dictionary's lookup table as uploaded (direct-indexed indexes: zeros)
+    if (X.gram_mode == 1) {
+        if (!digest(X.ghash_key, sizeof(uint64_t) * R.ghash_slots, vals[17]) ||
+            !digest(X.ghash_val, sizeof(uint32_t) * R.ghash_slots, vals[18]))
+            return -4;
+        vals[19] = X.ghash_bits;
+    }
+    const int m = std::max(0, std::min(n, 20));
+    for (int i = 0; i < m; ++i) out[i] = vals[i];
     return m;
 }
 
@@ -3191,10 +3206,14 @@ template <class T>
 bool put_array(std::FILE* f, const T* p, uint64_t n) {
     return std::fwrite(&n, sizeof n, 1, f) == 1 && (n == 0 || std::fwrite(p, sizeof(T), n, f) == n);
 }
+// `file_size`: the whole file's; a count whose elements the rest of the file cannot hold is
+// refused before anything is allocated for it
 template <class T>
-bool get_array(std::FILE* f, std::vector<T>& v, uint64_t max_n) {
+bool get_array(std::FILE* f, std::vector<T>& v, uint64_t max_n, uint64_t file_size) {
     uint64_t n = 0;
     if (std::fread(&n, sizeof n, 1, f) != 1 || n > max_n) return false;
+    const long pos = std::ftell(f);
+    if (pos < 0 || (uint64_t)pos > file_size || n > (file_size - (uint64_t)pos) / sizeof(T)) return false;
     v.resize(n);
     return n == 0 || std::fread(v.data(), sizeof(T), n, f) == n;
 }
@@ -3253,11 +3272,21 @@ NGS_API uint32_t ngsLoadIndex(const char* path) {
     char magic[8];
     uint32_t sc[9], valid[8];
     constexpr uint64_t kMax = uint64_t(1) << 40;
+    uint64_t fsz = 0;
+    {
+        const long end = std::fseek(f, 0, SEEK_END) == 0 ? std::ftell(f) : -1;
+        if (end < 0 || std::fseek(f, 0, SEEK_SET) != 0) {
+            std::fclose(f);
+            return 0;
+        }
+        fsz = (uint64_t)end;
+    }
     bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, kIndexMagic, 8) == 0 &&
               std::fread(sc, sizeof sc, 1, f) == 1 && std::fread(valid, sizeof valid, 1, f) == 1 &&
-              get_array(f, H.term_off, kMax) && get_array(f, H.term_bytes, kMax) && get_array(f, H.tk_off, kMax) &&
-              get_array(f, H.tk, kMax) && get_array(f, H.key_off, kMax) && get_array(f, H.key_bytes, kMax) &&
-              get_array(f, H.wild_w, kMax);
+              get_array(f, H.term_off, kMax, fsz) && get_array(f, H.term_bytes, kMax, fsz) &&
+              get_array(f, H.tk_off, kMax, fsz) && get_array(f, H.tk, kMax, fsz) &&
+              get_array(f, H.key_off, kMax, fsz) && get_array(f, H.key_bytes, kMax, fsz) &&
+              get_array(f, H.wild_w, kMax, fsz);
     std::fclose(f);
     if (!ok) return 0;
     H.csize = sc[0];

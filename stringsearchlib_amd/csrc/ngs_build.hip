@@ -4,7 +4,8 @@
 // per-gram hash SET, so a term is listed once per distinct gram) and :41-46 (buildGrams over
 // longLib, terms of >= 6 bytes, hpp:82-85). The host build (ngs_index.cpp) restates it with
 // threads; this is the same layout from the normalised terms already in HBM:
-//   1. k_gram_count   one thread per long term: its distinct 21-bit gram codes (count)
+//   1. k_gram_count   one thread per long term: its distinct 21-bit gram codes (count); a term
+//                     past kLaneTermChars characters is taken by its whole wave
 //   2. scan           exclusive prefix of the counts -> each term's slice of the pair array
 //   3. k_gram_emit    pairs (code << 32 | long-term id)
 //   4. radix sort     by (code, term): lists come out sorted by term id, as the kernels need
@@ -17,7 +18,8 @@
 // distinct keys, radix sort, unique); the host lays out its lookup table from them
 // (set_gram_dict); then steps 1-7 run with ids found by binary search over the keys in place of
 // the 21-bit codes, G = the number of keys.
-// Everything is bit-identical to the host build (tests/test_gpu_build.py compares digests).
+// Everything is bit-identical to the host build (tests/test_gpu_build.py compares digests;
+// tests/test_gpu_build_ref.py compares both with an independent model, array by array).
 #include <hipcub/hipcub.hpp>
 
 #include "ngs_build.h"
@@ -28,6 +30,14 @@ namespace {
 __device__ __forceinline__ uint32_t code3(const uint8_t* s) { return ((uint32_t)s[0] << 14) | ((uint32_t)s[1] << 7) | s[2]; }
 __device__ __forceinline__ bool ascii3(const uint8_t* s) { return !((s[0] | s[1] | s[2]) & 0x80); }
 
+// The first-occurrence scan is quadratic in the term's length: one lane takes terms of up to
+// kLaneTermChars characters; a longer term is taken by its whole wave, 64 positions at a time (a
+// 5,000-character term cost one lane 2.8 s). The order of a term's grams in its slice differs
+// between the two ways and does not matter: the slices are sorted as whole (gram, term) keys.
+constexpr uint64_t kLaneTermChars = 256;
+
+__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1; }
+
 // Distinct grams of long term t (ids n_short + t): the first occurrence of each code counts
 // (terms are ASCII; a gram with a byte >= 0x80 is skipped as in term_grams()).
 template <bool EMIT>
@@ -36,12 +46,12 @@ __global__ __launch_bounds__(256) void k_gram_terms(const uint64_t* __restrict__
                                                     uint32_t n_long, uint64_t* __restrict__ cnt,
                                                     const uint64_t* __restrict__ off, uint64_t* __restrict__ pairs) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_long) return;
-    const uint64_t a = term_off[n_short + t], L = term_off[n_short + t + 1] - a;
+    const bool live = t < n_long;  // every lane stays for the wave's long terms
+    const uint64_t a = live ? term_off[n_short + t] : 0, L = live ? term_off[n_short + t + 1] - a : 0;
     const uint8_t* s = bytes + a;
     uint32_t n = 0;
-    uint64_t o = EMIT ? off[t] : 0;
-    for (uint64_t i = 0; i + 2 < L; ++i) {
+    uint64_t o = (EMIT && live) ? off[t] : 0;
+    for (uint64_t i = 0; L <= kLaneTermChars && i + 2 < L; ++i) {
         if (!ascii3(s + i)) continue;
         const uint32_t c = code3(s + i);
         bool first = true;
@@ -50,7 +60,24 @@ __global__ __launch_bounds__(256) void k_gram_terms(const uint64_t* __restrict__
         if (EMIT) pairs[o++] = ((uint64_t)c << 32) | t;
         ++n;
     }
-    if (!EMIT) cnt[t] = n;
+    for (uint64_t todo = __ballot(L > kLaneTermChars); todo; todo &= todo - 1) {
+        const int src = __ffsll((unsigned long long)todo) - 1;
+        const uint64_t wa = __shfl(a, src), wL = __shfl(L, src), wo = __shfl(o, src);
+        const uint32_t wt = __shfl(t, src);
+        const uint8_t* ws = bytes + wa;
+        uint32_t total = 0;
+        for (uint64_t base = 0; base + 2 < wL; base += 64) {
+            const uint64_t i = base + (threadIdx.x & 63);
+            bool first = i + 2 < wL && ascii3(ws + i);
+            const uint32_t c = first ? code3(ws + i) : 0;
+            for (uint64_t j = 0; j < i && first; ++j) first = !(ascii3(ws + j) && code3(ws + j) == c);
+            const uint64_t m = __ballot(first);
+            if (EMIT && first) pairs[wo + total + __popcll(m & lanes_below())] = ((uint64_t)c << 32) | wt;
+            total += __popcll(m);
+        }
+        if ((int)(threadIdx.x & 63) == src) n = total;
+    }
+    if (!EMIT && live) cnt[t] = n;
 }
 
 // dictionary mode: the key of the g characters at character a (cs bytes each)
@@ -72,27 +99,46 @@ __global__ __launch_bounds__(256) void k_dict_terms(const uint64_t* __restrict__
                                                     uint64_t* __restrict__ out, const uint64_t* __restrict__ dict,
                                                     uint32_t nspace) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_long) return;
-    const uint64_t a = term_off[n_short + t], L = term_off[n_short + t + 1] - a;
+    const bool live = t < n_long;  // every lane stays for the wave's long terms (k_gram_terms)
+    const uint64_t a = live ? term_off[n_short + t] : 0, L = live ? term_off[n_short + t + 1] - a : 0;
     uint32_t n = 0;
-    uint64_t o = MODE ? off[t] : 0;
-    for (uint64_t i = 0; i + g <= L; ++i) {
-        const uint64_t k = gram_key_at(bytes, a + i, g, cs);
-        bool first = true;
-        for (uint64_t j = 0; j < i && first; ++j) first = gram_key_at(bytes, a + j, g, cs) != k;
-        if (!first) continue;
-        if (MODE == 1) out[o++] = k;
+    uint64_t o = (MODE && live) ? off[t] : 0;
+    auto put = [&](uint64_t at, uint64_t k, uint32_t term) {
+        if (MODE == 1) out[at] = k;
         if (MODE == 2) {
             uint32_t lo = 0, hi = nspace;  // lower_bound: the key is present
             while (lo < hi) {
                 const uint32_t m = (lo + hi) >> 1;
                 if (dict[m] < k) lo = m + 1; else hi = m;
             }
-            out[o++] = ((uint64_t)lo << 32) | t;
+            out[at] = ((uint64_t)lo << 32) | term;
         }
+    };
+    for (uint64_t i = 0; L <= kLaneTermChars && i + g <= L; ++i) {
+        const uint64_t k = gram_key_at(bytes, a + i, g, cs);
+        bool first = true;
+        for (uint64_t j = 0; j < i && first; ++j) first = gram_key_at(bytes, a + j, g, cs) != k;
+        if (!first) continue;
+        put(o++, k, t);
         ++n;
     }
-    if (MODE == 0) cnt[t] = n;
+    for (uint64_t todo = __ballot(L > kLaneTermChars); todo; todo &= todo - 1) {
+        const int src = __ffsll((unsigned long long)todo) - 1;
+        const uint64_t wa = __shfl(a, src), wL = __shfl(L, src), wo = __shfl(o, src);
+        const uint32_t wt = __shfl(t, src);
+        uint32_t total = 0;
+        for (uint64_t base = 0; base + g <= wL; base += 64) {
+            const uint64_t i = base + (threadIdx.x & 63);
+            bool first = i + g <= wL;
+            const uint64_t k = first ? gram_key_at(bytes, wa + i, g, cs) : 0;
+            for (uint64_t j = 0; j < i && first; ++j) first = gram_key_at(bytes, wa + j, g, cs) != k;
+            const uint64_t m = __ballot(first);
+            if (first) put(wo + total + __popcll(m & lanes_below()), k, wt);
+            total += __popcll(m);
+        }
+        if ((int)(threadIdx.x & 63) == src) n = total;
+    }
+    if (MODE == 0 && live) cnt[t] = n;
 }
 
 // Run boundaries of the sorted pairs: first / one-past-last index of every code present.

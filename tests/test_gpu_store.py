@@ -91,21 +91,13 @@ def test_load_refuses_bad_files(tmp_path):
 def _corruptions(data: bytes) -> dict:
     """Variants of a saved index file (layout: ngs_abi.cpp, "NGSIDX01" | 9 u32 scalars | 8 u32
     validChar words | arrays as u64 count + elements) that keep every count consistent."""
-    import struct
-    pos = 8 + 9 * 4 + 8 * 4
-    arrays = {}
-    for name, width in [("term_off", 8), ("term_bytes", 1), ("tk_off", 4), ("tk", 8), ("key_off", 8),
-                        ("key_bytes", 1), ("wild_w", 4)]:
-        (n,) = struct.unpack_from("<Q", data, pos)
-        arrays[name] = (pos + 8, n, width)
-        pos += 8 + n * width
-    assert pos == len(data)
+    import index_file
+    f = index_file.parse(data)  # walks the layout to the last byte
+    arrays = f.spans
     out = {}
 
     def patch(off, fmt, val):
-        b = bytearray(data)
-        struct.pack_into(fmt, b, off, val)
-        return bytes(b)
+        return index_file.patch(data, off, fmt, val)
 
     o, n, _ = arrays["term_off"]
     out["term_off_descending"] = patch(o + 8 * (n // 2), "<Q", 0)
@@ -115,8 +107,7 @@ def _corruptions(data: bytes) -> dict:
     out["tk_off_first_nonzero"] = patch(o, "<I", 1)
     o, n, _ = arrays["key_bytes"]
     out["key_without_nul"] = patch(o + n - 1, "<B", ord("X"))
-    out["short_term_len"] = patch(8 + 3 * 4, "<I", 5)
-    out["gram_mode"] = patch(8 + 2 * 4, "<I", 1)
-    (n_short,) = struct.unpack_from("<I", data, 8 + 7 * 4)
-    out["n_short"] = patch(8 + 7 * 4, "<I", n_short + 1)
+    out["short_term_len"] = patch(index_file.scalar_offset("short_term_len"), "<I", 5)
+    out["gram_mode"] = patch(index_file.scalar_offset("gram_mode"), "<I", 1)
+    out["n_short"] = patch(index_file.scalar_offset("n_short"), "<I", f.n_short + 1)
     return out
