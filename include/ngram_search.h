@@ -312,6 +312,93 @@ NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, ui
                                  uint32_t limit, float minSimilarity, uint32_t* counts, char*** results,
                                  float** scores, float** sims);
 
+/* ------------------------------------------------------------------------------------
+ * Self-join on the device: the near-duplicates of the library's own keys and their clusters (not
+ * in the reference). The key strings already lie in HBM, so "the library against itself" is a
+ * pipeline of stream-ordered stages in front of and behind ngsSearchDevice: the keys written as a
+ * query batch, the search, the key's own record removed, connected components over the (key, key)
+ * records that remain. Nothing goes through the host in between.
+ *
+ * The device entry points use the replica on the caller's current device and queue on `stream`.
+ * Arguments are checked before anything else: -3 bad argument (NULL pointers), then -1 bad handle,
+ * -2 un-built index, -3 a key range past ngsNumKeys, a capacity or stride too small, or no replica on
+ * the current device, -4 HIP error. ngsDropSelfDevice and ngsClusterDevice take no handle.
+ * ------------------------------------------------------------------------------------ */
+
+/* The bytes the keys [firstKey, firstKey + nKeys) occupy as a query batch: their characters without
+ * the NULs, times the character width. 0 for a bad handle, an un-built index or a range past
+ * ngsNumKeys (and for nKeys = 0). */
+NGS_API uint64_t ngsKeyQueryBytes(uint32_t handle, uint32_t firstKey, uint32_t nKeys);
+
+/* Writes those keys in ngsSearchDevice's query layout: query i is key firstKey + i as ngsKey / ngsKeyW
+ * returns it, without its NUL, at dBytes[dOffsets[i] .. dOffsets[i+1]); dOffsets[0..nKeys] ascend from 0
+ * (on a wide index the units are UTF-32, the offsets multiples of 4 and dBytes must be 4-byte aligned).
+ * Nothing past dBytes[ngsKeyQueryBytes(...)] is written. capBytes below ngsKeyQueryBytes(...) or a range
+ * past the keys: -3. nKeys = 0 is valid (firstKey up to ngsNumKeys), writes dOffsets[0] = 0 only and
+ * reads nothing of the index but the offset entry of firstKey. Stream-ordered, no host wait. */
+NGS_API int ngsKeyQueriesDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys, uint8_t* dBytes,
+                                uint64_t capBytes, uint64_t* dOffsets, void* stream);
+
+/* Per row i < n of a result block (ngsSearchDevice's layout), in place: the record whose key id is
+ * firstKey + i is removed if there is one (at most one exists, wherever it stands) and the records
+ * behind it move up by one; the row is cut to `limit` records (0: no cut); dCounts[i] is the new count.
+ * A count above `stride` is read as `stride`. Cells past the new count are unspecified; nothing beyond
+ * i * stride + stride is written. Stream-ordered, no host wait. 0, -3 (NULL dCounts; NULL dKeys or
+ * dScores with n and stride non-zero), -4 HIP error. */
+NGS_API int ngsDropSelfDevice(uint32_t* dCounts, uint32_t* dKeys, float* dScores, uint32_t n, uint32_t stride,
+                              uint32_t firstKey, uint32_t limit, void* stream);
+
+/* The join of keys [firstKey, firstKey + nKeys): row i (dCounts[i], records at i * outStride) is the
+ * answer ngsSearchDevice gives for the string of key firstKey + i over the library without that key:
+ * the full ranking at `threshold` with the key's own record removed, then the first `limit` (0: all).
+ * That is the search with limit + 1 and the key's own record dropped, whether or not it is among the
+ * hits (a key need not find itself: a zero or negative weight, a string the validChar set blanks).
+ * It runs ngsKeyQueriesDevice into the call's own scratch, ngsSearchDevice with that limit into the
+ * caller's block and ngsDropSelfDevice. outStride must be at least
+ * min((limit ? limit : 2^31-1) + 1, ngsNumKeys), one more than the search of the same limit asks, for
+ * the record that is found and removed: anything less is -3. The queries are normalised with the
+ * handle's current validChar set, like any query. Returns when the results are complete; return codes
+ * as ngsSearchDevice. */
+NGS_API int ngsSelfJoinDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                              uint32_t outStride, uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream);
+
+/* Connected components. The block is read as undirected edges (firstKey + i, dKeys[i * stride + r]),
+ * r < min(dCounts[i], stride); an edge with an end >= nLabels is ignored and nothing is read through
+ * that id. NGS_CLUSTER_INIT first sets dLabels[k] = k for k < nLabels; NGS_CLUSTER_FINISH afterwards
+ * makes dLabels[k] the smallest id of k's component. Without FINISH dLabels is a forest with
+ * dLabels[k] <= k that later calls merge further blocks into; n = 0 with a flag is valid (init only,
+ * finish only). The result does not depend on the order the edges arrive in: it is exactly
+ * reproducible. Stream-ordered, no host wait. 0, -3 (an unknown flag, NULL dLabels with nLabels, NULL
+ * dCounts or dKeys with n and stride non-zero), -4 HIP error. */
+#define NGS_CLUSTER_INIT 1u
+#define NGS_CLUSTER_FINISH 2u
+NGS_API int ngsClusterDevice(const uint32_t* dCounts, const uint32_t* dKeys, uint32_t n, uint32_t stride,
+                             uint32_t firstKey, uint32_t* dLabels, uint32_t nLabels, uint32_t flags, void* stream);
+
+/* The join of keys [firstKey, firstKey + nKeys) into caller-allocated arrays: counts[nKeys], row i's
+ * records (key ids, scores) at i * stride, stride >= min(limit ? limit : 2^31-1, ngsNumKeys). Runs on
+ * the first replica in batches of at most 65,536 keys and returns the total number of records. On
+ * failure (unknown handle, un-built index, range past the keys, stride too small, HIP error) it returns
+ * 0, zeroes the counts and sets ngsLastError. */
+NGS_API uint32_t selfJoin(uint32_t handle, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                          uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
+
+/* Clusters of near-duplicate keys: labels[ngsNumKeys] (caller-allocated), labels[k] = the smallest key
+ * id of k's cluster. The edges are the records of the self-join at (threshold, limit), limit in
+ * 1..4,096; with minSimilarity > -1.0f only those whose edit-distance similarity (above: the key's
+ * string as the query) is at least minSimilarity. batchKeys: keys per batch (0 = 65,536); the label
+ * array stays on the device across the batches and is finished and read back once. The filter keeps
+ * a record unless its similarity is below minSimilarity, in the search's order; it is not
+ * ngsRerankDevice (no sort, no cap on the stride). What the similarity's special values mean for it:
+ * a key of more than 4,096 normalised characters has -1.0f ("not computed") on all of its own row's
+ * records, so with a filter it gives no edge (other keys' rows may still link to it); the key "*" is a
+ * wildcard query with similarity 1.0f on every record, so its row keeps all of them; the similarity
+ * is never NaN (a NaN would be kept). Returns the number
+ * of clusters; 0 with ngsLastError set when the limit is 0 (a HIP invalid-value code) or above 4,096
+ * (NGS_ERR_RERANK_LIMIT), minSimilarity is NaN, the handle is unknown or un-built, or HIP fails. */
+NGS_API uint32_t dedupKeys(uint32_t handle, float threshold, uint32_t limit, float minSimilarity,
+                           uint32_t batchKeys, uint32_t* labels);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);

@@ -178,6 +178,22 @@ def lib():
         L.scoreBatchSimW.argtypes = [u32, C.POINTER(W), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PW), PF, PF]
         L.scoreBatchSimU8.restype = u32
         L.scoreBatchSimU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF, PF]
+    if hasattr(L, "ngsSelfJoinDevice"):  # (experiment builds of older sources lack the self-join)
+        vp = C.c_void_p
+        L.ngsKeyQueryBytes.restype = u64
+        L.ngsKeyQueryBytes.argtypes = [u32, u32, u32]
+        L.ngsKeyQueriesDevice.restype = C.c_int
+        L.ngsKeyQueriesDevice.argtypes = [u32, u32, u32, vp, u64, vp, vp]
+        L.ngsDropSelfDevice.restype = C.c_int
+        L.ngsDropSelfDevice.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp]
+        L.ngsSelfJoinDevice.restype = C.c_int
+        L.ngsSelfJoinDevice.argtypes = [u32, u32, u32, f32, u32, u32, vp, vp, vp, vp]
+        L.ngsClusterDevice.restype = C.c_int
+        L.ngsClusterDevice.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
+        L.selfJoin.restype = u32
+        L.selfJoin.argtypes = [u32, u32, u32, f32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(f32)]
+        L.dedupKeys.restype = u32
+        L.dedupKeys.argtypes = [u32, f32, u32, f32, u32, C.POINTER(u32)]
     if hasattr(L, "ngsServeState"):
         L.ngsServeState.restype = C.c_int
         L.ngsServeState.argtypes = [u32]

@@ -27,6 +27,7 @@
 #include "../../include/ngram_search.h"
 #include "ngs_build.h"
 #include "ngs_index.h"
+#include "ngs_join.h"
 #include "ngs_kernels.h"
 #include "ngs_sim.h"
 #include "ngs_utf8.h"
@@ -683,7 +684,7 @@ bool upload_replica(Library& L, Replica& R, bool keys_unique, bool first) {
     PhaseTimer pt;
     bool ok = dev_upload(&term_off, H.term_off, R.owned) && dev_upload(&term_bytes, H.term_bytes, R.owned, 8) /* whole dwords, and a short term's second dword (myers_short) */ &&
               dev_upload(&tk_off, H.tk_off, R.owned) && dev_upload(&tk, H.tk, R.owned) &&
-              dev_upload(&key_off, H.key_off, R.owned) && dev_upload(&key_bytes, kb, R.owned) &&
+              dev_upload(&key_off, H.key_off, R.owned) && dev_upload(&key_bytes, kb, R.owned, 4) /* whole dwords (k_key_queries) */ &&
               dev_upload(&wild_w, H.wild_w, R.owned);
     if (!ok) return false;
     pt.mark("replica: arrays to HBM");
@@ -2587,6 +2588,160 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
     std::copy(sv.begin(), sv.end(), *sims);
     return total;
 }
+
+// ---- the self-join (ngsKeyQueriesDevice .. dedupKeys) ----
+
+// keys [first, first + n) lie in the index
+bool join_range_ok(const Library& L, uint32_t first, uint32_t n) {
+    return (uint64_t)first + n <= L.host.n_keys;
+}
+uint64_t join_query_bytes(const Library& L, uint32_t first, uint32_t n) {
+    return join_query_off(L.host.key_off.data(), first, n, L.host.csize);
+}
+// the limit the join's search runs with: one more than the caller's, for the record that is found
+// and removed (limit 0: every key)
+uint32_t join_search_limit(const Library& L, uint32_t limit) {
+    const uint64_t want = (uint64_t)(limit ? limit : kInt32Max) + 1u;
+    return (uint32_t)std::min<uint64_t>(want, L.host.n_keys);
+}
+
+// One batch of the join on replica R (its device current, lock and BatchGuard held by the caller):
+// the keys gathered into d_raw / d_off, the search with one record more, the key's own record
+// dropped. The results are complete on return when `wait`; else drop-self is queued on s.
+int join_batch(Library& L, Replica& R, uint32_t first, uint32_t n, float thr, uint32_t limit, uint32_t stride,
+               uint8_t* d_raw, uint64_t* d_off, uint32_t* d_n, uint32_t* d_k, float* d_s, hipStream_t s, bool wait) {
+    if (!HIP_CHECK(launch_key_queries(R.dev, first, n, join_query_bytes(L, first, n), d_raw, d_off, s))) return -4;
+    if (const int rc = search_on_replica(L, R, d_raw, d_off, n, thr, join_search_limit(L, limit), stride, d_n, d_k, d_s, s))
+        return rc;
+    if (!HIP_CHECK(launch_drop_self(d_n, d_k, d_s, n, stride, first, limit, s))) return -4;
+    return !wait || HIP_CHECK(hipStreamSynchronize(s)) ? 0 : -4;
+}
+
+// keys per batch of a host join: at most `want` (0: kJoinBatchKeys), and a result block within kOutBudget
+uint32_t join_batch_keys(uint32_t want, uint32_t nk, uint32_t Ls) {
+    const size_t fit = std::max<size_t>(1, kOutBudget / (sizeof(uint32_t) + sizeof(float)) / std::max(Ls, 1u));
+    return (uint32_t)std::min<size_t>({want ? want : kJoinBatchKeys, std::max(nk, 1u), fit});
+}
+
+uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr, uint32_t limit, uint32_t stride,
+                        uint32_t* counts, uint32_t* key_ids, float* scores) {
+    if (counts) std::fill(counts, counts + nk, 0u);
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    auto fail = [&](int err) -> uint32_t {  // (counts may hold finished batches by then)
+        if (err && !t_last_error) t_last_error = err;
+        if (counts) std::fill(counts, counts + nk, 0u);
+        return 0;
+    };
+    if (!L || !L->host.indexed || !counts || !join_range_ok(*L, first, nk)) return fail((int)hipErrorInvalidValue);
+    const uint32_t Lm = effective_limit(*L, limit);
+    if (stride < Lm || (nk && Lm && (!key_ids || !scores))) return fail((int)hipErrorInvalidValue);
+    if (nk == 0 || Lm == 0) return 0;
+    BatchGuard bg(L);
+    Replica& R = *L->reps.front();
+    if (!HIP_CHECK(hipSetDevice(R.device))) return fail(0);
+    const uint32_t Ls = join_search_limit(*L, limit);
+    const uint32_t B = join_batch_keys(0, nk, Ls);
+    // a batch's records come back packed ({key id, score bits} in row order behind the rows' offsets,
+    // as ngsPackResults writes them): the bytes read back follow the records, not keys x stride
+    SimBuffers M;
+    uint8_t *d_raw = nullptr, *d_tmp = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t *d_n = nullptr, *d_k = nullptr, *d_pos = nullptr, *d_rec = nullptr;
+    float* d_s = nullptr;
+    uint64_t raw_cap = 0;
+    for (uint32_t k0 = first; k0 < first + nk; k0 += B)
+        raw_cap = std::max(raw_cap, join_query_bytes(*L, k0, std::min(B, first + nk - k0)));
+    const size_t tmp_bytes = std::max<size_t>(pack_pairs_temp_bytes(B), 1 << 16);
+    if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_raw, raw_cap + 16) ||
+        !M.alloc(&d_off, (size_t)B + 1) || !M.alloc(&d_n, B) || !M.alloc(&d_k, (size_t)B * Ls) ||
+        !M.alloc(&d_s, (size_t)B * Ls) || !M.alloc(&d_pos, (size_t)B + 1) || !M.alloc(&d_rec, 2 * (size_t)B * Ls) ||
+        !M.alloc(&d_tmp, tmp_bytes))
+        return fail(0);
+    std::vector<uint32_t> h_pos((size_t)B + 1), h_rec;
+    uint64_t total = 0;
+    for (uint32_t done = 0; done < nk; done += B) {
+        const uint32_t n = std::min(B, nk - done);
+        if (join_batch(*L, R, first + done, n, thr, limit, Ls, d_raw, d_off, d_n, d_k, d_s, M.stream, false) != 0)
+            return fail(kErrInternal);
+        if (!HIP_CHECK(launch_pack_pairs(d_n, d_k, d_s, n, Ls, d_pos, d_rec, d_tmp, tmp_bytes, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_pos.data(), d_pos, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost,
+                                      M.stream)) ||
+            !HIP_CHECK(hipStreamSynchronize(M.stream)))
+            return fail(0);
+        const uint32_t recs = h_pos[n];
+        h_rec.resize(2 * (size_t)recs);
+        if (recs && (!HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, sizeof(uint32_t) * 2 * recs, hipMemcpyDeviceToHost,
+                                               M.stream)) ||
+                     !HIP_CHECK(hipStreamSynchronize(M.stream))))
+            return fail(0);
+        for (uint32_t i = 0; i < n; ++i) {  // (a row keeps at most min(limit, keys) <= stride records)
+            const uint32_t c = h_pos[i + 1] - h_pos[i];
+            const uint32_t* rec = h_rec.data() + 2 * (size_t)h_pos[i];
+            uint32_t* k = key_ids + (size_t)(done + i) * stride;
+            float* sc = scores + (size_t)(done + i) * stride;
+            for (uint32_t r = 0; r < c; ++r) {
+                k[r] = rec[2 * r];
+                std::memcpy(sc + r, rec + 2 * r + 1, sizeof(float));
+            }
+            counts[done + i] = c;
+        }
+        total += recs;
+    }
+    if (total > 0xFFFFFFFFull) return fail((int)hipErrorInvalidValue);  // (the return value is 32-bit)
+    return (uint32_t)total;
+}
+
+uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, uint32_t batch_keys, uint32_t* labels) {
+    if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim) {
+        t_last_error = labels && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
+        return 0;
+    }
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L || !L->host.indexed) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    const uint32_t nk = L->host.n_keys;
+    if (nk == 0) return 0;
+    BatchGuard bg(L);
+    Replica& R = *L->reps.front();
+    if (!HIP_CHECK(hipSetDevice(R.device))) return 0;
+    const uint32_t Ls = join_search_limit(*L, limit);
+    const uint32_t B = join_batch_keys(batch_keys, nk, Ls);
+    const bool verify = min_sim > -1.0f;  // every similarity is >= -1: nothing to filter at or below it
+    SimBuffers M;
+    uint8_t* d_raw = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t *d_n = nullptr, *d_k = nullptr, *d_lab = nullptr;
+    float *d_s = nullptr, *d_v = nullptr;
+    uint64_t raw_cap = 0;
+    for (uint32_t k0 = 0; k0 < nk; k0 += B) raw_cap = std::max(raw_cap, join_query_bytes(*L, k0, std::min(B, nk - k0)));
+    if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_raw, raw_cap + 16) ||
+        !M.alloc(&d_off, (size_t)B + 1) || !M.alloc(&d_n, B) || !M.alloc(&d_k, (size_t)B * Ls) ||
+        !M.alloc(&d_s, (size_t)B * Ls) || !M.alloc(&d_lab, nk) || (verify && !M.alloc(&d_v, (size_t)B * Ls)))
+        return 0;
+    // the label array stays on the device across the batches: finished and read back once
+    for (uint32_t done = 0; done < nk; done += B) {
+        const uint32_t n = std::min(B, nk - done);
+        if (join_batch(*L, R, done, n, thr, limit, Ls, d_raw, d_off, d_n, d_k, d_s, M.stream, false) != 0) {
+            if (!t_last_error) t_last_error = kErrInternal;
+            return 0;
+        }
+        if (verify && (queue_similarity(*L, R, d_raw, d_off, n, Ls, d_n, d_k, d_s, d_v, false, 0.0f, M.stream) != 0 ||
+                       !HIP_CHECK(launch_keep_similar(d_n, d_k, d_s, d_v, n, Ls, min_sim, M.stream))))
+            return 0;
+        const uint32_t flags = (done == 0 ? kClusterInit : 0u) | (done + n == nk ? kClusterFinish : 0u);
+        if (!HIP_CHECK(launch_cluster(d_n, d_k, n, Ls, done, d_lab, nk, flags, M.stream))) return 0;
+    }
+    if (!HIP_CHECK(hipMemcpyAsync(labels, d_lab, sizeof(uint32_t) * nk, hipMemcpyDeviceToHost, M.stream)) ||
+        !HIP_CHECK(hipStreamSynchronize(M.stream)))
+        return 0;
+    uint32_t clusters = 0;
+    for (uint32_t k = 0; k < nk; ++k) clusters += labels[k] == k;
+    return clusters;
+}
 }  // namespace
 }  // namespace ngs
 
@@ -3087,6 +3242,75 @@ NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, ui
                                  uint32_t limit, float minSimilarity, uint32_t* counts, char*** results, float** scores,
                                  float** sims) {
     return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, true);
+}
+
+NGS_API uint64_t ngsKeyQueryBytes(uint32_t handle, uint32_t firstKey, uint32_t nKeys) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L || !L->host.indexed || !join_range_ok(*L, firstKey, nKeys)) return 0;
+    return join_query_bytes(*L, firstKey, nKeys);
+}
+
+NGS_API int ngsKeyQueriesDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys, uint8_t* dBytes, uint64_t capBytes,
+                                uint64_t* dOffsets, void* stream) {
+    if (!dOffsets || (capBytes && !dBytes)) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L) return -1;
+    if (!L->host.indexed) return -2;
+    if (!join_range_ok(*L, firstKey, nKeys)) return -3;
+    const uint64_t total = join_query_bytes(*L, firstKey, nKeys);
+    if (capBytes < total || (L->host.csize == 4 && (reinterpret_cast<uintptr_t>(dBytes) & 3u))) return -3;
+    Replica* R = nullptr;
+    if (const int rc = sim_entry(handle, L, R)) return rc;
+    BatchGuard bg(L);
+    return HIP_CHECK(launch_key_queries(R->dev, firstKey, nKeys, total, dBytes, dOffsets, (hipStream_t)stream)) ? 0 : -4;
+}
+
+NGS_API int ngsDropSelfDevice(uint32_t* dCounts, uint32_t* dKeys, float* dScores, uint32_t n, uint32_t stride,
+                              uint32_t firstKey, uint32_t limit, void* stream) {
+    if (!dCounts || (n && stride && (!dKeys || !dScores))) return -3;
+    return HIP_CHECK(launch_drop_self(dCounts, dKeys, dScores, n, stride, firstKey, limit, (hipStream_t)stream)) ? 0 : -4;
+}
+
+NGS_API int ngsSelfJoinDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                              uint32_t outStride, uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream) {
+    if (!dCounts || (nKeys && (!dKeys || !dScores))) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    const int rc = sim_entry(handle, L, R);
+    if (rc == -1 || rc == -2) return rc;
+    if (!join_range_ok(*L, firstKey, nKeys) || outStride < join_search_limit(*L, limit)) return -3;
+    if (rc) return rc;
+    if (nKeys == 0) return 0;
+    BatchGuard bg(L);
+    // the call's own scratch: the gathered queries, released once the search has read them
+    SimBuffers M;
+    uint8_t* d_raw = nullptr;
+    uint64_t* d_off = nullptr;
+    if (!M.alloc(&d_raw, join_query_bytes(*L, firstKey, nKeys) + 16) || !M.alloc(&d_off, (size_t)nKeys + 1)) return -4;
+    return join_batch(*L, *R, firstKey, nKeys, threshold, limit, outStride, d_raw, d_off, dCounts, dKeys, dScores,
+                      (hipStream_t)stream, true);
+}
+
+NGS_API int ngsClusterDevice(const uint32_t* dCounts, const uint32_t* dKeys, uint32_t n, uint32_t stride,
+                             uint32_t firstKey, uint32_t* dLabels, uint32_t nLabels, uint32_t flags, void* stream) {
+    if ((flags & ~(kClusterInit | kClusterFinish)) || (nLabels && !dLabels) || (n && stride && (!dCounts || !dKeys)))
+        return -3;
+    return HIP_CHECK(launch_cluster(dCounts, dKeys, n, stride, firstKey, dLabels, nLabels, flags, (hipStream_t)stream))
+               ? 0
+               : -4;
+}
+
+NGS_API uint32_t selfJoin(uint32_t handle, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                          uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores) {
+    return self_join_host(handle, firstKey, nKeys, threshold, limit, stride, counts, keyIds, scores);
+}
+
+NGS_API uint32_t dedupKeys(uint32_t handle, float threshold, uint32_t limit, float minSimilarity, uint32_t batchKeys,
+                           uint32_t* labels) {
+    return dedup_host(handle, threshold, limit, minSimilarity, batchKeys, labels);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

@@ -297,6 +297,84 @@ class StringIndex:
         if rc:
             raise RuntimeError(f"ngsRerankDevice failed: {rc}")
 
+    # -- self-join: near-duplicate keys and their clusters (include/ngram_search.h) ----------
+    def self_join(self, first: int = 0, count: int | None = None, threshold: float = 0.0, limit: int = 10):
+        """selfJoin: for each key first .. first + count - 1 (default: to the last key) the list of
+        (key_id, score) the search gives for the key's own string, over the library without that key."""
+        L = _native.lib()
+        nk = self.num_keys()
+        n = max(0, nk - first) if count is None else count
+        stride = max(1, min(limit if limit else INT32_MAX, nk))
+        counts = (C.c_uint32 * max(1, n))()
+        keys = (C.c_uint32 * max(1, n * stride))()
+        scores = (C.c_float * max(1, n * stride))()
+        L.ngsLastError(1)
+        total = L.selfJoin(self.handle, first, n, threshold, limit, stride, counts, keys, scores)
+        if not total:
+            _check("selfJoin")
+        out = [list(zip(keys[i * stride:i * stride + counts[i]], scores[i * stride:i * stride + counts[i]]))
+               for i in range(n)]
+        assert sum(map(len, out)) == total
+        return out
+
+    def dedup(self, threshold: float, limit: int = 10, min_similarity: float | None = None, batch_keys: int = 0):
+        """dedupKeys: labels[k] = the smallest key id of key k's cluster, the clusters being the
+        connected components of the self-join at (threshold, limit); with min_similarity, of its records
+        whose edit-distance similarity is at least that. limit in 1..4,096."""
+        L = _native.lib()
+        nk = self.num_keys()
+        labels = (C.c_uint32 * max(1, nk))()
+        L.ngsLastError(1)
+        clusters = L.dedupKeys(self.handle, threshold, limit, -1.0 if min_similarity is None else min_similarity,
+                               batch_keys, labels)
+        if not clusters:
+            _check("dedupKeys")
+        out = list(labels[:nk])
+        assert clusters == sum(1 for k, v in enumerate(out) if k == v)
+        return out
+
+    def key_query_bytes(self, first: int, count: int) -> int:
+        """ngsKeyQueryBytes: the bytes keys first .. first + count - 1 take as a query batch."""
+        return _native.lib().ngsKeyQueryBytes(self.handle, first, count)
+
+    def key_queries_device(self, first: int, count: int, d_bytes: int, cap_bytes: int, d_offsets: int,
+                           stream: int = 0) -> None:
+        """ngsKeyQueriesDevice on raw device pointers: those keys in search_device's query layout, queued
+        on `stream`."""
+        rc = _native.lib().ngsKeyQueriesDevice(self.handle, first, count, d_bytes or None, cap_bytes, d_offsets,
+                                               stream or None)
+        if rc:
+            raise RuntimeError(f"ngsKeyQueriesDevice failed: {rc}")
+
+    @staticmethod
+    def drop_self_device(d_counts: int, d_keys: int, d_scores: int, n: int, stride: int, first: int, limit: int = 0,
+                         stream: int = 0) -> None:
+        """ngsDropSelfDevice on raw device pointers: row i loses the record of key first + i and is cut to
+        `limit` (0: no cut), in place; queued on `stream`."""
+        rc = _native.lib().ngsDropSelfDevice(d_counts, d_keys or None, d_scores or None, n, stride, first, limit,
+                                             stream or None)
+        if rc:
+            raise RuntimeError(f"ngsDropSelfDevice failed: {rc}")
+
+    def self_join_device(self, first: int, count: int, threshold: float, limit: int, out_stride: int, d_counts: int,
+                         d_keys: int, d_scores: int, stream: int = 0) -> None:
+        """ngsSelfJoinDevice on raw device pointers; out_stride >= min((limit or 2^31-1) + 1, keys)."""
+        rc = _native.lib().ngsSelfJoinDevice(self.handle, first, count, threshold, limit, out_stride, d_counts,
+                                             d_keys or None, d_scores or None, stream or None)
+        if rc:
+            raise RuntimeError(f"ngsSelfJoinDevice failed: {rc}")
+
+    @staticmethod
+    def cluster_device(d_counts: int, d_keys: int, n: int, stride: int, first: int, d_labels: int, n_labels: int,
+                       init: bool = True, finish: bool = True, stream: int = 0) -> None:
+        """ngsClusterDevice on raw device pointers: the block's (first + i, key) records merged into the
+        label forest d_labels[n_labels]; `init` sets labels[k] = k first, `finish` makes every label the
+        smallest id of its component. Queued on `stream`."""
+        rc = _native.lib().ngsClusterDevice(d_counts or None, d_keys or None, n, stride, first, d_labels or None,
+                                            n_labels, (1 if init else 0) | (2 if finish else 0), stream or None)
+        if rc:
+            raise RuntimeError(f"ngsClusterDevice failed: {rc}")
+
     def search_device_async(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int,
                             out_stride: int, d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> int:
         """ngsSearchDeviceAsync: queues the search and returns its ticket (wait_device(ticket))."""
