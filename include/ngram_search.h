@@ -399,6 +399,78 @@ NGS_API uint32_t selfJoin(uint32_t handle, uint32_t firstKey, uint32_t nKeys, fl
 NGS_API uint32_t dedupKeys(uint32_t handle, float threshold, uint32_t limit, float minSimilarity,
                            uint32_t batchKeys, uint32_t* labels);
 
+/* ------------------------------------------------------------------------------------
+ * The similarity by a metric, and the term that matched (not in the reference). Q (length m), T
+ * (length L >= 1), the wildcard rule, the cap of 4,096 normalised characters, "a count above the
+ * stride reads as the stride" and "key id >= ngsNumKeys is -1.0f" are exactly those of the
+ * edit-distance similarity above. The metric selects d and the divisor:
+ *   NGS_SIM_LEVENSHTEIN  d = Levenshtein, sim = 1.0f - (float)d / (float)max(m, L): the bits of the
+ *                        entry points without a metric;
+ *   NGS_SIM_OSA          optimal string alignment: Levenshtein plus the swap of two adjacent
+ *                        characters at cost 1, no substring edited twice:
+ *                        D[i][j] = min(D[i-1][j] + 1, D[i][j-1] + 1, D[i-1][j-1] + [Q_i != T_j],
+ *                                      D[i-2][j-2] + 1 if Q_i = T_{j-1} and Q_{i-1} = T_j);
+ *                        sim = 1.0f - (float)d / (float)max(m, L); an empty Q has d = L, sim 0.0f;
+ *   NGS_SIM_PARTIAL      d = the least Levenshtein(Q, T[a..b)) over 0 <= a <= b <= L (both ends of T
+ *                        free, the empty substring allowed, so d <= m);
+ *                        sim = 1.0f - (float)d / (float)m for m >= 1, 0.0f for m = 0. It is directional:
+ *                        Q inside T scores 1.0f, T inside Q does not.
+ * Each is one correctly rounded fp32 division and one subtraction. A record's similarity is the
+ * largest over the key's non-empty terms. The matched term is the term id (0 .. getSize - 1, see
+ * ngsTerm) that attains it, the smallest id among several of the same fp32 value, and 0xFFFFFFFF
+ * where no term was compared: wildcard rows, -1.0f rows, a key without a non-empty term.
+ * An unknown metric is a bad argument (-3), checked with the other arguments before the handle.
+ * ------------------------------------------------------------------------------------ */
+#define NGS_SIM_LEVENSHTEIN 0u
+#define NGS_SIM_OSA 1u
+#define NGS_SIM_PARTIAL 2u
+
+/* ngsSimilarityDevice by `metric`; dTerms (may be NULL: not wanted, and then nothing is spent on it)
+ * receives the matched term ids in dSim's layout. Return codes as ngsSimilarityDevice. */
+NGS_API int ngsSimilarityDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                 uint32_t nQueries, uint32_t stride, const uint32_t* dCounts,
+                                 const uint32_t* dKeys, uint32_t metric, float* dSim, uint32_t* dTerms,
+                                 void* stream);
+
+/* ngsRerankDevice by `metric`; dTerms (may be NULL) is filled and permuted in place with dKeys,
+ * dScores and dSim. Return codes as ngsRerankDevice. */
+NGS_API int ngsRerankDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                             uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys,
+                             float* dScores, float* dSim, uint32_t* dTerms, uint32_t metric,
+                             float minSimilarity, void* stream);
+
+/* scoreBatchSim / scoreBatchSimW / scoreBatchSimU8 by `metric`. With terms != NULL, *terms is a fourth
+ * flat new[]'d array, terms[j] the matched term id of results[j]: free it with ngsReleaseTerms. An
+ * unknown metric fails like a NaN minSimilarity: 0, counts zeroed, outputs untouched, ngsLastError a
+ * HIP invalid-value code. Everything else as scoreBatchSim. */
+NGS_API uint32_t scoreBatchSimM(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                                uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
+                                char*** results, float** scores, float** sims, uint32_t** terms);
+NGS_API uint32_t scoreBatchSimMW(uint32_t handle, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                 uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
+                                 wchar_t*** results, float** scores, float** sims, uint32_t** terms);
+NGS_API uint32_t scoreBatchSimMU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                                  uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
+                                  char*** results, float** scores, float** sims, uint32_t** terms);
+/* delete[]s the fourth array of scoreBatchSimM*; NULL is allowed. */
+NGS_API void ngsReleaseTerms(uint32_t* terms);
+
+/* dedupKeys with the filter's similarity by `metric` (an unknown one: 0 and a HIP invalid-value code).
+ * The special values are handled as dedupKeys documents. NGS_SIM_PARTIAL is directional: the row of
+ * key a measures a's string inside key b's terms, the row of b the reverse, and an edge is made if
+ * either row keeps its record, as for any record. */
+NGS_API uint32_t dedupKeysM(uint32_t handle, float threshold, uint32_t limit, uint32_t metric, float minSimilarity,
+                            uint32_t batchKeys, uint32_t* labels);
+
+/* The normalised term `termId` (0 .. getSize(handle) - 1) as the index holds it: bytes on a narrow
+ * index, UTF-32 units on a wide one, no terminator. Returns its length in characters whatever capBytes
+ * is (size a buffer with buf = NULL, capBytes = 0) and copies min(capBytes, length x width) bytes,
+ * rounded down to whole characters, into buf. The terms live in device memory only: every call is one
+ * small synchronous copy from the first replica, a diagnostic-rate call for showing results, not for
+ * bulk export. -1 bad handle, -2 un-built index, -3 id out of range (or NULL buf with a capacity),
+ * -4 HIP error. */
+NGS_API int64_t ngsTerm(uint32_t handle, uint32_t termId, void* buf, uint64_t capBytes);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);

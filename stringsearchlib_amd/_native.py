@@ -178,6 +178,28 @@ def lib():
         L.scoreBatchSimW.argtypes = [u32, C.POINTER(W), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PW), PF, PF]
         L.scoreBatchSimU8.restype = u32
         L.scoreBatchSimU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF, PF]
+    if hasattr(L, "ngsSimilarityDeviceM"):  # (experiment builds of older sources lack the metrics)
+        vp = C.c_void_p
+        PF, PT = C.POINTER(C.POINTER(f32)), C.POINTER(C.POINTER(u32))
+        L.ngsSimilarityDeviceM.restype = C.c_int
+        L.ngsSimilarityDeviceM.argtypes = [u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]
+        L.ngsRerankDeviceM.restype = C.c_int
+        L.ngsRerankDeviceM.argtypes = [u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, f32, vp]
+        L.scoreBatchSimM.restype = u32
+        L.scoreBatchSimM.argtypes = [u32, C.POINTER(cp), u32, f32, u32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF,
+                                     PF, PT]
+        L.scoreBatchSimMW.restype = u32
+        L.scoreBatchSimMW.argtypes = [u32, C.POINTER(W), u32, f32, u32, u32, f32, C.POINTER(u32), C.POINTER(PW), PF,
+                                      PF, PT]
+        L.scoreBatchSimMU8.restype = u32
+        L.scoreBatchSimMU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, u32, f32, C.POINTER(u32), C.POINTER(PP),
+                                       PF, PF, PT]
+        L.ngsReleaseTerms.restype = None
+        L.ngsReleaseTerms.argtypes = [C.POINTER(u32)]
+        L.dedupKeysM.restype = u32
+        L.dedupKeysM.argtypes = [u32, f32, u32, u32, f32, u32, C.POINTER(u32)]
+        L.ngsTerm.restype = C.c_int64
+        L.ngsTerm.argtypes = [u32, u32, vp, u64]
     if hasattr(L, "ngsSelfJoinDevice"):  # (experiment builds of older sources lack the self-join)
         vp = C.c_void_p
         L.ngsKeyQueryBytes.restype = u64

@@ -2446,8 +2446,11 @@ bool sim_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint3
 }
 
 // Queues the similarity kernel (and, with `rerank`, the re-rank behind it) on s; nothing waits.
+// use_m: the M entry points' launchers (metric, and the matched terms in d_t when not null); the
+// entry points without a metric keep the launchers they had.
 int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
-                     uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, bool rerank, float min_sim, hipStream_t s) {
+                     uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, bool rerank, float min_sim, hipStream_t s,
+                     bool use_m = false, uint32_t metric = kSimLevenshtein, uint32_t* d_t = nullptr) {
     if (n == 0) return 0;
     bool ok = true;
     const uint32_t* key_term = sim_key_term(R, ok);
@@ -2456,6 +2459,12 @@ int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_
     {
         std::lock_guard<std::mutex> g(L.valid_mu);
         std::memcpy(valid, L.valid, sizeof valid);
+    }
+    if (use_m) {
+        if (!HIP_CHECK(launch_similarity_m(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, metric, d_v, d_t, s)))
+            return -4;
+        if (rerank && !HIP_CHECK(launch_rerank_m(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
+        return 0;
     }
     if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, d_v, s))) return -4;
     if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, min_sim, s))) return -4;
@@ -2495,15 +2504,18 @@ constexpr size_t kSimChunkRecords = size_t(1) << 22;  // records (query x limit)
 // behind it on the same stream, then counts, key ids, scores and sims read back and the result
 // pointers built as marshal() builds every other call's. u8: UTF-8 queries on a wide index
 // (decoded on the host), the strings of the UTF-8 key table. The first replica answers.
+// use_m: scoreBatchSimM*: the similarity by `metric`, and with terms != null the matched term ids as
+// a fourth flat array (ngsReleaseTerms).
 template <typename CharT>
 uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, float thr, uint32_t limit, float min_sim,
-                   uint32_t* counts, CharT*** results, float** scores, float** sims, bool u8) {
+                   uint32_t* counts, CharT*** results, float** scores, float** sims, bool u8, bool use_m = false,
+                   uint32_t metric = kSimLevenshtein, uint32_t** terms = nullptr) {
     if (counts) std::fill(counts, counts + nq, 0u);
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = find_lib(handle);
     const uint32_t cs = u8 ? (uint32_t)sizeof(uint32_t) : (uint32_t)sizeof(CharT);
     if (!L || !L->host.indexed || !queries || !counts || !results || !scores || !sims || L->host.csize != cs) return 0;
-    if (min_sim != min_sim) {
+    if (min_sim != min_sim || metric >= kSimMetrics) {
         t_last_error = (int)hipErrorInvalidValue;
         return 0;
     }
@@ -2532,13 +2544,15 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
     const uint32_t chunk = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, kSimChunkRecords / Lm));
     SimBuffers M;
     uint64_t* d_off = nullptr;
-    uint32_t *d_n = nullptr, *d_k = nullptr;
+    uint32_t *d_n = nullptr, *d_k = nullptr, *d_t = nullptr;
     float *d_s = nullptr, *d_v = nullptr;
     const size_t recs = (size_t)chunk * Lm;
     if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_off, (size_t)chunk + 1) ||
-        !M.alloc(&d_n, chunk) || !M.alloc(&d_k, recs) || !M.alloc(&d_s, recs) || !M.alloc(&d_v, recs))
+        !M.alloc(&d_n, chunk) || !M.alloc(&d_k, recs) || !M.alloc(&d_s, recs) || !M.alloc(&d_v, recs) ||
+        (terms && !M.alloc(&d_t, recs)))
         return 0;
     std::vector<uint32_t> cnt(nq, 0), keys, h_n(chunk), h_k(recs);  // (counts stay zero unless the whole call succeeds)
+    std::vector<uint32_t> tv, h_t(terms ? recs : 0);
     std::vector<float> sc, sv, h_s(recs), h_v(recs);
     std::vector<uint64_t> h_off((size_t)chunk + 1);
     std::vector<uint8_t> h_raw;
@@ -2563,13 +2577,17 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (queue_similarity(*L, R, d_raw, d_off, B, Lm, d_n, d_k, d_s, d_v, true, min_sim, M.stream) != 0) return 0;
+        if (queue_similarity(*L, R, d_raw, d_off, B, Lm, d_n, d_k, d_s, d_v, true, min_sim, M.stream, use_m, metric,
+                             d_t) != 0)
+            return 0;
         // 4. everything back
         const size_t rb = (size_t)B * Lm;
         if (!HIP_CHECK(hipMemcpyAsync(h_n.data(), d_n, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_k.data(), d_k, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_s.data(), d_s, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_v.data(), d_v, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            (terms &&
+             !HIP_CHECK(hipMemcpyAsync(h_t.data(), d_t, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream))) ||
             !HIP_CHECK(hipStreamSynchronize(M.stream)))
             return 0;
         for (uint32_t i = 0; i < B; ++i) {
@@ -2579,6 +2597,7 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
             keys.insert(keys.end(), h_k.begin() + at, h_k.begin() + at + c);
             sc.insert(sc.end(), h_s.begin() + at, h_s.begin() + at + c);
             sv.insert(sv.end(), h_v.begin() + at, h_v.begin() + at + c);
+            if (terms) tv.insert(tv.end(), h_t.begin() + at, h_t.begin() + at + c);
         }
     }
     // 5. the result pointers, and the third flat array
@@ -2586,6 +2605,10 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
     const uint32_t total = marshal(*L, keys, sc, results, scores, T);
     *sims = new float[std::max<size_t>(sv.size(), 1)];
     std::copy(sv.begin(), sv.end(), *sims);
+    if (terms) {
+        *terms = new uint32_t[std::max<size_t>(tv.size(), 1)];
+        std::copy(tv.begin(), tv.end(), *terms);
+    }
     return total;
 }
 
@@ -2692,8 +2715,9 @@ uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr,
     return (uint32_t)total;
 }
 
-uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, uint32_t batch_keys, uint32_t* labels) {
-    if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim) {
+uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, uint32_t batch_keys, uint32_t* labels,
+                    bool use_m = false, uint32_t metric = kSimLevenshtein) {
+    if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim || metric >= kSimMetrics) {
         t_last_error = labels && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
         return 0;
     }
@@ -2729,7 +2753,8 @@ uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, u
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (verify && (queue_similarity(*L, R, d_raw, d_off, n, Ls, d_n, d_k, d_s, d_v, false, 0.0f, M.stream) != 0 ||
+        if (verify && (queue_similarity(*L, R, d_raw, d_off, n, Ls, d_n, d_k, d_s, d_v, false, 0.0f, M.stream, use_m,
+                                        metric) != 0 ||
                        !HIP_CHECK(launch_keep_similar(d_n, d_k, d_s, d_v, n, Ls, min_sim, M.stream))))
             return 0;
         const uint32_t flags = (done == 0 ? kClusterInit : 0u) | (done + n == nk ? kClusterFinish : 0u);
@@ -3244,6 +3269,82 @@ NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, ui
     return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, true);
 }
 
+NGS_API int ngsSimilarityDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                 uint32_t nQueries, uint32_t stride, const uint32_t* dCounts, const uint32_t* dKeys,
+                                 uint32_t metric, float* dSim, uint32_t* dTerms, void* stream) {
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || metric >= kSimMetrics) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = sim_entry(handle, L, R)) return rc;
+    BatchGuard bg(L);
+    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
+                            const_cast<uint32_t*>(dKeys), nullptr, dSim, false, 0.0f, (hipStream_t)stream, true, metric,
+                            dTerms);
+}
+
+NGS_API int ngsRerankDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                             uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
+                             float* dSim, uint32_t* dTerms, uint32_t metric, float minSimilarity, void* stream) {
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
+        stride > kRerankMaxStride || minSimilarity != minSimilarity || metric >= kSimMetrics)
+        return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = sim_entry(handle, L, R)) return rc;
+    BatchGuard bg(L);
+    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, true,
+                            minSimilarity, (hipStream_t)stream, true, metric, dTerms);
+}
+
+NGS_API uint32_t scoreBatchSimM(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                                uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts, char*** results,
+                                float** scores, float** sims, uint32_t** terms) {
+    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false,
+                     true, metric, terms);
+}
+
+NGS_API uint32_t scoreBatchSimMW(uint32_t handle, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                 uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
+                                 wchar_t*** results, float** scores, float** sims, uint32_t** terms) {
+    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false,
+                     true, metric, terms);
+}
+
+NGS_API uint32_t scoreBatchSimMU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
+                                  uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
+                                  char*** results, float** scores, float** sims, uint32_t** terms) {
+    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, true,
+                     true, metric, terms);
+}
+
+NGS_API void ngsReleaseTerms(uint32_t* terms) { delete[] terms; }
+
+NGS_API int64_t ngsTerm(uint32_t handle, uint32_t termId, void* buf, uint64_t capBytes) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L) return -1;
+    if (!L->host.indexed) return -2;
+    if (termId >= L->host.n_terms) return -3;
+    BatchGuard bg(L);
+    Replica& R = *L->reps.front();
+    int cur = 0;
+    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
+    struct Back {  // the caller's device is current again on return
+        int dev;
+        ~Back() { (void)hipSetDevice(dev); }
+    } back{cur};
+    if (!HIP_CHECK(hipSetDevice(R.device))) return -4;
+    uint64_t span[2] = {0, 0};  // term_off holds character offsets
+    if (!HIP_CHECK(hipMemcpy(span, R.dev.term_off + termId, sizeof span, hipMemcpyDeviceToHost))) return -4;
+    const uint64_t len = span[1] - span[0], cs = L->host.csize;
+    const uint64_t take = std::min(capBytes / cs, len);
+    if (take && !buf) return -3;
+    if (take && !HIP_CHECK(hipMemcpy(buf, R.dev.term_bytes + span[0] * cs, take * cs, hipMemcpyDeviceToHost))) return -4;
+    return (int64_t)len;
+}
+
 NGS_API uint64_t ngsKeyQueryBytes(uint32_t handle, uint32_t firstKey, uint32_t nKeys) {
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = find_lib(handle);
@@ -3311,6 +3412,11 @@ NGS_API uint32_t selfJoin(uint32_t handle, uint32_t firstKey, uint32_t nKeys, fl
 NGS_API uint32_t dedupKeys(uint32_t handle, float threshold, uint32_t limit, float minSimilarity, uint32_t batchKeys,
                            uint32_t* labels) {
     return dedup_host(handle, threshold, limit, minSimilarity, batchKeys, labels);
+}
+
+NGS_API uint32_t dedupKeysM(uint32_t handle, float threshold, uint32_t limit, uint32_t metric, float minSimilarity,
+                            uint32_t batchKeys, uint32_t* labels) {
+    return dedup_host(handle, threshold, limit, minSimilarity, batchKeys, labels, true, metric);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

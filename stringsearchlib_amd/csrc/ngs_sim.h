@@ -11,6 +11,14 @@
 // key's terms. Wildcard queries score kSimWildcard on every record; a query of more than
 // kSimMaxQuery characters, or a key id outside the index, kSimNone ("not computed").
 //
+//
+// The M entry points select d and the divisor by a metric: kSimLevenshtein is the
+// above; kSimOsa adds the adjacent transposition at cost 1 (optimal string alignment: no substring
+// is edited twice), same divisor; kSimPartial is the semi-global form, d = the least Levenshtein
+// distance of Q to any substring of T (the empty one included, so d <= m), sim = 1 - d / m for
+// m >= 1 and 0 for m = 0. The matched term is the term id that attains a record's similarity, the
+// smallest such id; kSimNoTerm where no term was compared.
+//
 // Plain C++17 without a HIP include: g++ compiles the host routines alone (tests/sanitize).
 #pragma once
 
@@ -32,6 +40,9 @@ constexpr uint32_t kSimMaxQuery = 4096;     // normalised query characters the k
 constexpr uint32_t kRerankMaxStride = 4096; // records per query ngsRerankDevice sorts (LDS: 8 bytes each)
 constexpr float kSimWildcard = 1.0f;
 constexpr float kSimNone = -1.0f;
+constexpr uint32_t kSimLevenshtein = 0, kSimOsa = 1, kSimPartial = 2;  // NGS_SIM_* of the public header
+constexpr uint32_t kSimMetrics = 3;
+constexpr uint32_t kSimNoTerm = 0xFFFFFFFFu;  // "no term was compared"
 
 // ---- normalisation of one character (the one-liners of ngs_kernels.hip, restated) ----
 NGS_HD inline bool sim_space(uint32_t c) { return c == 32u || (c >= 9u && c <= 13u); }
@@ -90,11 +101,50 @@ NGS_HD inline int myers_step(MyersBlock& b, uint64_t eq, int hin, uint64_t top) 
     return hout;
 }
 
+// The same block with the adjacent transposition (Hyyro's OSA extension). d0: the rows of the
+// previous column whose diagonal delta was 0; eqp: the previous column's eq. A row i may take the
+// transposition when Q_i = T_{j-1} (eqp), Q_{i-1} = T_j (eq, one row up) and D[i-1][j-1] was not
+// reached by a zero diagonal (~d0, one row up). The row above a block's first row is the last row
+// of the block above: its bit comes in as tin and this block's bit 63 goes out as tout (0 / 1),
+// beside hin / hout. The first block takes tin = 0.
+struct OsaBlock : MyersBlock {
+    uint64_t d0 = 0, eqp = 0;
+};
+NGS_HD inline int osa_step(OsaBlock& b, uint64_t eq, int hin, uint32_t tin, uint64_t top, uint32_t& tout) {
+    const uint64_t neg = hin < 0 ? 1ull : 0ull;
+    uint64_t xv = eq | b.mv;
+    const uint64_t eqn = eq | neg;
+    uint64_t xh = (((eqn & b.pv) + b.pv) ^ b.pv) | eqn;
+    const uint64_t x = ~b.d0 & eq;
+    const uint64_t tr = ((x << 1) | (uint64_t)tin) & b.eqp;
+    xh |= tr;
+    xv |= tr;
+    tout = (uint32_t)(x >> 63);
+    b.d0 = xh | b.mv;
+    b.eqp = eq;
+    uint64_t ph = b.mv | ~(xh | b.pv);
+    uint64_t mh = b.pv & xh;
+    const int hout = (ph & top) ? 1 : ((mh & top) ? -1 : 0);
+    ph = (ph << 1) | (hin > 0 ? 1ull : 0ull);
+    mh = (mh << 1) | neg;
+    b.pv = mh | ~(xv | ph);
+    b.mv = ph & xv;
+    return hout;
+}
+
 // the fp32 similarity of a distance
 NGS_HD inline float sim_value(uint32_t d, uint32_t m, uint32_t L) {
     const uint32_t mx = m > L ? m : L;
     if (mx == 0) return 1.0f;  // (no term is empty; two empty strings are equal)
     return 1.0f - (float)d / (float)mx;
+}
+// ... of kSimPartial's distance: the divisor is the query's length
+NGS_HD inline float sim_value_partial(uint32_t d, uint32_t m) {
+    if (m == 0) return 0.0f;
+    return 1.0f - (float)d / (float)m;
+}
+NGS_HD inline float sim_value_metric(uint32_t metric, uint32_t d, uint32_t m, uint32_t L) {
+    return metric == kSimPartial ? sim_value_partial(d, m) : sim_value(d, m, L);
 }
 
 // ---- host reference routines (the device kernels restate them over LDS tables) ----
@@ -137,6 +187,81 @@ inline uint32_t lev_myers_blocks(QF q, uint32_t m, TF t, uint32_t L) {
     return score;
 }
 
+// the rows of query word w (of W) matching character c
+template <class QF>
+inline uint64_t sim_word_eq(QF q, uint32_t w, uint32_t rows, uint32_t c) {
+    uint64_t eq = 0;
+    for (uint32_t i = 0; i < rows; ++i) eq |= q(64u * w + i) == c ? 1ull << i : 0ull;
+    return eq;
+}
+
+// kSimOsa's d(Q, T), one word (m <= 64)
+template <class QF, class TF>
+inline uint32_t osa_myers64(QF q, uint32_t m, TF t, uint32_t L) {
+    if (m == 0) return L;
+    const uint64_t top = 1ull << (m - 1u);
+    OsaBlock b;
+    uint32_t score = m, tout = 0;
+    for (uint32_t j = 0; j < L; ++j) score += (uint32_t)osa_step(b, sim_word_eq(q, 0, m, t(j)), +1, 0u, top, tout);
+    return score;
+}
+
+// ... any m <= kSimMaxQuery: hout and tout carried from block to block within a column
+template <class QF, class TF>
+inline uint32_t osa_myers_blocks(QF q, uint32_t m, TF t, uint32_t L) {
+    if (m == 0) return L;
+    if (m > kSimMaxQuery) return 0xFFFFFFFFu;
+    const uint32_t W = (m + 63u) / 64u;
+    OsaBlock blk[kSimMaxQuery / 64];
+    uint32_t score = m;
+    for (uint32_t j = 0; j < L; ++j) {
+        const uint32_t c = t(j);
+        int h = +1;
+        uint32_t tr = 0;
+        for (uint32_t w = 0; w < W; ++w) {
+            const uint32_t rows = w + 1 < W ? 64u : m - 64u * w;
+            h = osa_step(blk[w], sim_word_eq(q, w, rows, c), h, tr, 1ull << (rows - 1u), tr);
+        }
+        score += (uint32_t)h;
+    }
+    return score;
+}
+
+// kSimPartial's d(Q, T): row 0 of every column is 0 (hin = 0 into the first block), and d is the
+// least of the last row over columns 0 .. L (column 0 holds m)
+template <class QF, class TF>
+inline uint32_t partial_myers64(QF q, uint32_t m, TF t, uint32_t L) {
+    if (m == 0) return 0;
+    const uint64_t top = 1ull << (m - 1u);
+    MyersBlock b;
+    uint32_t score = m, best = m;
+    for (uint32_t j = 0; j < L; ++j) {
+        score += (uint32_t)myers_step(b, sim_word_eq(q, 0, m, t(j)), 0, top);
+        if (score < best) best = score;
+    }
+    return best;
+}
+
+template <class QF, class TF>
+inline uint32_t partial_myers_blocks(QF q, uint32_t m, TF t, uint32_t L) {
+    if (m == 0) return 0;
+    if (m > kSimMaxQuery) return 0xFFFFFFFFu;
+    const uint32_t W = (m + 63u) / 64u;
+    MyersBlock blk[kSimMaxQuery / 64];
+    uint32_t score = m, best = m;
+    for (uint32_t j = 0; j < L; ++j) {
+        const uint32_t c = t(j);
+        int h = 0;
+        for (uint32_t w = 0; w < W; ++w) {
+            const uint32_t rows = w + 1 < W ? 64u : m - 64u * w;
+            h = myers_step(blk[w], sim_word_eq(q, w, rows, c), h, 1ull << (rows - 1u));
+        }
+        score += (uint32_t)h;
+        if (score < best) best = score;
+    }
+    return best;
+}
+
 // ---- the wide short path's match-mask table: open addressing over kSimSlots slots ----
 constexpr uint32_t kSimSlots = 128;            // <= 64 distinct characters: at most half full
 constexpr uint32_t kSimEmpty = 0xFFFFFFFFu;    // no normalised character (they are <= 0x10FFFF)
@@ -157,9 +282,17 @@ NGS_HD inline uint64_t rerank_key(uint32_t sim_bits, uint32_t pos) {
 hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term,
                              const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
                              const uint32_t* counts, const uint32_t* keys, float* sim, hipStream_t s);
+// ... by `metric` (< kSimMetrics), and with terms != null the matched term ids in sim's layout
+hipError_t launch_similarity_m(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term,
+                               const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
+                               const uint32_t* counts, const uint32_t* keys, uint32_t metric, float* sim,
+                               uint32_t* terms, hipStream_t s);
 // per query: records with sim < min_sim dropped, the rest ordered (sim desc, position asc), in place
 hipError_t launch_rerank(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
                          float min_sim, hipStream_t s);
+// ... the matched terms (may be null) permuted with them
+hipError_t launch_rerank_m(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
+                           uint32_t* terms, float min_sim, hipStream_t s);
 // key_term[k] = the term of key k's pair (kSimEmpty: none) of an index whose keys have one pair each
 hipError_t build_key_term(const DevIndex& X, uint32_t* key_term, hipStream_t s);
 #endif

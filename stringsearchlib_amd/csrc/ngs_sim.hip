@@ -10,6 +10,9 @@
 //             (its 64 characters in registers) and takes the horizontal delta lane w - 1 produced
 //             one step earlier.
 // k_rerank: one workgroup per query sorts (sim desc, position asc) in LDS and permutes in place.
+// The metric (ngs_sim.h: Levenshtein, OSA, partial) and the matched-term output are template
+// parameters of k_sim, the term array one of k_rerank: the entry points of §9.2
+// launch the instantiations <wide, kSimLevenshtein, false> and <false>, which are what they were.
 #include <hip/hip_runtime.h>
 
 #include "ngs_common.h"
@@ -24,6 +27,7 @@ struct SimArgs {
     const uint32_t* counts;
     const uint32_t* keys;
     float* sim;
+    uint32_t* terms;           // kTerms: the matched term ids, in sim's layout
     const uint32_t* key_term;  // indexes without kt_off: the term of each key
     uint32_t n, stride;
     ValidSet V;
@@ -47,16 +51,43 @@ __device__ __forceinline__ uint32_t term_at(const DevIndex& X, const uint32_t* k
     return X.kt_off ? X.kt_term[j] : key_term[key];
 }
 
+// The recurrence's state and one column of it by metric (ngs_sim.h): kSimOsa carries two more words
+// and the transposition bit between blocks; kSimPartial is the Levenshtein step behind hin = 0.
+template <uint32_t kMetric>
+struct SimBlock : MyersBlock {};
+template <>
+struct SimBlock<kSimOsa> : OsaBlock {};
+template <uint32_t kMetric>
+__device__ __forceinline__ int sim_step(SimBlock<kMetric>& b, uint64_t eq, int hin, uint32_t tin, uint64_t top,
+                                        uint32_t& tout) {
+    if constexpr (kMetric == kSimOsa) return osa_step(b, eq, hin, tin, top, tout);
+    else return myers_step(b, eq, hin, top);
+}
+template <uint32_t kMetric>
+constexpr int kSimTopDelta = kMetric == kSimPartial ? 0 : +1;  // the horizontal delta of row 0
+// the score after a column: kSimPartial keeps the least over the columns in `low`
+template <uint32_t kMetric>
+__device__ __forceinline__ void sim_column(uint32_t& score, uint32_t& low, int hout) {
+    score += (uint32_t)hout;
+    if constexpr (kMetric == kSimPartial) low = min(low, score);
+}
+template <uint32_t kMetric>
+__device__ __forceinline__ float sim_of(uint32_t d, uint32_t m, uint32_t L) {
+    if constexpr (kMetric == kSimPartial) return sim_value_partial(d, m);
+    else return sim_value(d, m, L);
+}
+
 // d(Q, T) of a narrow term through the byte-indexed mask table: the term is read a dword at a
 // time with the next one in flight, as myers_match_t does (term_bytes is padded by two dwords)
+template <uint32_t kMetric>
 __device__ __forceinline__ uint32_t myers_narrow(const uint64_t* peq, uint32_t m, const uint8_t* tb, uint64_t a,
                                                  uint32_t L) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(tb + (a & ~(uint64_t)3));
     const uint32_t skip = (uint32_t)(a & 3u);
     uint32_t cur = w[0] >> (8u * skip), nxt = skip + L > 4u ? w[1] : 0u;
-    uint32_t avail = 4u - skip, k = 1, score = m;
+    uint32_t avail = 4u - skip, k = 1, score = m, low = m, tout = 0;
     const uint64_t top = 1ull << (m - 1u);
-    MyersBlock b;
+    SimBlock<kMetric> b;
     for (uint32_t j = 0; j < L; ++j) {
         if (!avail) {
             cur = nxt;
@@ -67,9 +98,9 @@ __device__ __forceinline__ uint32_t myers_narrow(const uint64_t* peq, uint32_t m
         const uint32_t c = cur & 255u;
         cur >>= 8;
         --avail;
-        score += (uint32_t)myers_step(b, peq[c], +1, top);
+        sim_column<kMetric>(score, low, sim_step<kMetric>(b, peq[c], kSimTopDelta<kMetric>, 0u, top, tout));
     }
-    return score;
+    return kMetric == kSimPartial ? low : score;
 }
 
 // the wide table: kSimSlots masks, then kSimSlots keys; a character not in it matches no row
@@ -82,20 +113,35 @@ __device__ __forceinline__ uint64_t wide_mask(const uint64_t* mask, const uint32
         s = (s + 1u) & (kSimSlots - 1u);
     }
 }
+template <uint32_t kMetric>
 __device__ __forceinline__ uint32_t myers_wide(const uint64_t* mask, const uint32_t* slot_key, uint32_t m,
                                                const uint32_t* t, uint32_t L) {
     const uint64_t top = 1ull << (m - 1u);
-    MyersBlock b;
-    uint32_t score = m, nxt = t[0];
+    SimBlock<kMetric> b;
+    uint32_t score = m, low = m, tout = 0, nxt = t[0];
     for (uint32_t j = 0; j < L; ++j) {
         const uint32_t c = nxt;
         if (j + 1u < L) nxt = t[j + 1u];
-        score += (uint32_t)myers_step(b, wide_mask(mask, slot_key, c), +1, top);
+        sim_column<kMetric>(score, low,
+                            sim_step<kMetric>(b, wide_mask(mask, slot_key, c), kSimTopDelta<kMetric>, 0u, top, tout));
     }
-    return score;
+    return kMetric == kSimPartial ? low : score;
 }
 
-template <bool kWide>
+// a record's best term so far: the larger similarity, and with kTerms the smaller term id among equals
+template <bool kTerms>
+__device__ __forceinline__ void sim_take(float& best, uint32_t& best_t, float v, uint32_t t) {
+    if constexpr (kTerms) {
+        if (v > best || (v == best && t < best_t)) {
+            best = v;
+            best_t = t;
+        }
+    } else {
+        best = fmaxf(best, v);
+    }
+}
+
+template <bool kWide, uint32_t kMetric = kSimLevenshtein, bool kTerms = false>
 __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
     constexpr uint32_t cs = kWide ? 4u : 1u;
     __shared__ uint64_t s_mask[256];             // narrow: by byte; wide: slots [0, kSimSlots)
@@ -109,6 +155,7 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
     if (count == 0) return;
     const uint32_t* keys = A.keys + (size_t)q * A.stride;
     float* out = A.sim + (size_t)q * A.stride;
+    uint32_t* out_t = kTerms ? A.terms + (size_t)q * A.stride : nullptr;
     const uint64_t qa = A.off[q], qe = A.off[q + 1];
     const uint64_t n = qe > qa ? (qe - qa) / cs : 0;
     const uint8_t* rq = A.raw + qa;
@@ -147,7 +194,10 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
         }
     }
     if (is_fixed) {
-        for (uint32_t r = lane; r < count; r += 64) out[r] = fixed;
+        for (uint32_t r = lane; r < count; r += 64) {
+            out[r] = fixed;
+            if constexpr (kTerms) out_t[r] = kSimNoTerm;
+        }
         return;
     }
     const uint32_t m = (uint32_t)m64;
@@ -183,52 +233,61 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
         // rounds of 64 records; the next round's key -> term -> offsets chain is issued before
         // the current round's recurrence
         uint32_t key = lane < count ? keys[lane] : kSimEmpty;
-        uint32_t j = 0, je = 0;
+        uint32_t j = 0, je = 0, tt = kSimNoTerm;  // tt: the term [ta, tb) belongs to (read with kTerms)
         uint64_t ta = 0, tb = 0;
-        auto first_term = [&](uint32_t k, uint32_t& fj, uint32_t& fje, uint64_t& fa, uint64_t& fb) {
+        auto first_term = [&](uint32_t k, uint32_t& fj, uint32_t& fje, uint64_t& fa, uint64_t& fb, uint32_t& ft) {
             fj = fje = 0;
             fa = fb = 0;
+            ft = kSimNoTerm;
             if (k >= X.n_keys) return;
             key_terms(X, k, fj, fje);
             if (fj >= fje) return;
             const uint32_t t = term_at(X, A.key_term, k, fj);
             if (t >= X.n_terms) return;
+            ft = t;
             fa = X.term_off[t];
             fb = X.term_off[t + 1];
         };
-        first_term(key, j, je, ta, tb);
+        first_term(key, j, je, ta, tb, tt);
         for (uint32_t base = 0; base < count; base += 64) {
             const uint32_t r = base + lane, rn = r + 64;
             const uint32_t nkey = rn < count ? keys[rn] : kSimEmpty;
-            uint32_t nj, nje;
+            uint32_t nj, nje, nt;
             uint64_t na, nb;
-            first_term(nkey, nj, nje, na, nb);
+            first_term(nkey, nj, nje, na, nb, nt);
             float best = kSimNone;
+            uint32_t best_t = kSimNoTerm;
             while (j < je) {
                 if (tb > ta) {
                     const uint32_t L = (uint32_t)(tb - ta);
-                    uint32_t d = L;  // an empty Q: L insertions
+                    uint32_t d = kMetric == kSimPartial ? 0u : L;  // an empty Q: L insertions (partial: none)
                     if (m) {
-                        if (kWide) d = myers_wide(s_mask, s_key, m, reinterpret_cast<const uint32_t*>(X.term_bytes) + ta, L);
-                        else d = myers_narrow(s_mask, m, X.term_bytes, ta, L);
+                        if (kWide)
+                            d = myers_wide<kMetric>(s_mask, s_key, m, reinterpret_cast<const uint32_t*>(X.term_bytes) + ta, L);
+                        else d = myers_narrow<kMetric>(s_mask, m, X.term_bytes, ta, L);
                     }
-                    best = fmaxf(best, sim_value(d, m, L));
+                    sim_take<kTerms>(best, best_t, sim_of<kMetric>(d, m, L), tt);
                 }
                 if (++j < je) {
                     const uint32_t t = term_at(X, A.key_term, key, j);
                     ta = tb = 0;
                     if (t < X.n_terms) {
+                        tt = t;
                         ta = X.term_off[t];
                         tb = X.term_off[t + 1];
                     }
                 }
             }
-            if (r < count) out[r] = best;
+            if (r < count) {
+                out[r] = best;
+                if constexpr (kTerms) out_t[r] = best_t;
+            }
             key = nkey;
             j = nj;
             je = nje;
             ta = na;
             tb = nb;
+            tt = nt;
         }
         return;
     }
@@ -252,6 +311,7 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
     for (uint32_t r = 0; r < count; ++r) {
         const uint32_t key = keys[r];
         float best = kSimNone;
+        uint32_t best_t = kSimNoTerm;
         uint32_t j = 0, je = 0;
         if (key < X.n_keys) key_terms(X, key, j, je);
         for (; j < je; ++j) {
@@ -260,14 +320,19 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
             const uint64_t ta = X.term_off[t];
             const uint32_t L = (uint32_t)(X.term_off[t + 1] - ta);
             if (!L) continue;
-            MyersBlock b;
-            uint32_t score = m;  // followed by lane W - 1
-            int hout = 0;
+            SimBlock<kMetric> b;
+            uint32_t score = m, low = m;  // followed by lane W - 1
+            int hout = 0;  // kSimOsa: the transposition bit rides in bit 2 of hout + 1
             const uint32_t steps = L + W - 1u;
             for (uint32_t s = 0; s < steps; ++s) {
                 // lane w is at term character s - w, with the delta lane w - 1 left at it one step ago
                 const int up = __shfl_up(hout, 1);
-                const int hin = lane == 0 ? +1 : up;
+                int hin = lane == 0 ? kSimTopDelta<kMetric> : up;
+                uint32_t tin = 0, tout = 0;
+                if constexpr (kMetric == kSimOsa) {
+                    tin = lane == 0 ? 0u : (uint32_t)up >> 2;
+                    hin = lane == 0 ? +1 : (int)((uint32_t)up & 3u) - 1;
+                }
                 const uint32_t at = s - lane;
                 if (lane < W && at < L) {  // (s < lane wraps past L)
                     const uint32_t c = ld_char(X.term_bytes, ta + at, cs);
@@ -277,14 +342,18 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
                         const uint32_t qi = kWide ? qw[i] : (qw[i >> 2] >> (8u * (i & 3u))) & 255u;
                         eq |= qi == c ? 1ull << i : 0ull;
                     }
-                    hout = myers_step(b, eq & rowmask, hin, top);
-                    if (lane == W - 1u) score += (uint32_t)hout;
+                    hout = sim_step<kMetric>(b, eq & rowmask, hin, tin, top, tout);
+                    if (lane == W - 1u) sim_column<kMetric>(score, low, hout);
+                    if constexpr (kMetric == kSimOsa) hout = (hout + 1) | (int)(tout << 2);
                 }
             }
-            const uint32_t d = (uint32_t)__shfl((int)score, (int)(W - 1u));
-            best = fmaxf(best, sim_value(d, m, L));
+            const uint32_t d = (uint32_t)__shfl((int)(kMetric == kSimPartial ? low : score), (int)(W - 1u));
+            sim_take<kTerms>(best, best_t, sim_of<kMetric>(d, m, L), t);
         }
-        if (lane == 0) out[r] = best;
+        if (lane == 0) {
+            out[r] = best;
+            if constexpr (kTerms) out_t[r] = best_t;
+        }
     }
 }
 
@@ -309,8 +378,11 @@ __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int mask) {
     return ((uint64_t)hi << 32) | lo;
 }
 
+// kTerms: a fourth array, the matched term ids, moves with the records
+template <bool kTerms>
 __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint32_t* __restrict__ counts,
-                                                            uint32_t* keys, float* scores, float* sim, float min_sim) {
+                                                            uint32_t* keys, float* scores, float* sim, float min_sim,
+                                                            uint32_t* terms) {
     extern __shared__ uint64_t s_rec[];  // rerank_pow2(stride) sort keys
     __shared__ uint32_t s_kept;
     const uint32_t tid = threadIdx.x, q = blockIdx.x, nthreads = blockDim.x;
@@ -318,6 +390,7 @@ __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint
     uint32_t* k = keys + (size_t)q * stride;
     float* sc = scores + (size_t)q * stride;
     float* sv = sim + (size_t)q * stride;
+    uint32_t* tv = kTerms ? terms + (size_t)q * stride : nullptr;
     if (count <= 64) {
         // one wave, no barrier: every lane holds its record, the sort runs through shuffles, and
         // a lane fetches the record of its new position from the lane that loaded it
@@ -325,6 +398,8 @@ __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint
         const bool live = tid < count;
         const uint32_t rk = live ? k[tid] : 0u;
         const float rs = live ? sc[tid] : 0.0f, rv = live ? sv[tid] : 0.0f;
+        uint32_t rt = 0;
+        if constexpr (kTerms) rt = live ? tv[tid] : 0u;
         uint64_t rec = live && !(rv < min_sim) ? rerank_key(__float_as_uint(rv), tid) : kRerankDropped;
         for (uint32_t k2 = 2; k2 <= 64; k2 <<= 1)
             for (uint32_t j = k2 >> 1; j > 0; j >>= 1) {
@@ -336,10 +411,13 @@ __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint
         const int src = (int)((uint32_t)rec & 63u);
         const uint32_t ok = (uint32_t)__shfl((int)rk, src);
         const float os = __shfl(rs, src), ov = __shfl(rv, src);
+        uint32_t ot = 0;
+        if constexpr (kTerms) ot = (uint32_t)__shfl((int)rt, src);
         if (tid < kept) {
             k[tid] = ok;
             sc[tid] = os;
             sv[tid] = ov;
+            if constexpr (kTerms) tv[tid] = ot;
         }
         if (tid == 0) counts[q] = kept;
         return;
@@ -377,6 +455,7 @@ __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint
     // in place: every record is read into registers before any is written
     uint32_t mk[kRerankPer];
     float ms[kRerankPer], mv[kRerankPer];
+    uint32_t mt[kTerms ? kRerankPer : 1u];
 #pragma unroll
     for (uint32_t u = 0; u < kRerankPer; ++u) {
         const uint32_t i = tid + u * nthreads;
@@ -387,6 +466,7 @@ __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint
             mk[u] = k[p];
             ms[u] = sc[p];
             mv[u] = sv[p];
+            if constexpr (kTerms) mt[u] = tv[p];
         }
     }
     // the loads of every wave have returned (s_waitcnt 0: this wave's outstanding memory operations
@@ -401,6 +481,7 @@ __global__ __launch_bounds__(kRerankThreads) void k_rerank(uint32_t stride, uint
             k[i] = mk[u];
             sc[i] = ms[u];
             sv[i] = mv[u];
+            if constexpr (kTerms) tv[i] = mt[u];
         }
     }
     if (tid == 0) counts[q] = kept;
@@ -424,22 +505,58 @@ hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const u
                              const uint32_t* keys, float* sim, hipStream_t s) {
     if (!n || !stride) return hipSuccess;
     if (!X.kt_off && !key_term) return hipErrorInvalidValue;
-    SimArgs A{raw, off, counts, keys, sim, key_term, n, stride, {}};
+    SimArgs A{raw, off, counts, keys, sim, nullptr, key_term, n, stride, {}};
     for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
     if (X.csize == 4) hipLaunchKernelGGL(k_sim<true>, dim3(n), dim3(64), 0, s, X, A);
     else hipLaunchKernelGGL(k_sim<false>, dim3(n), dim3(64), 0, s, X, A);
     return hipGetLastError();
 }
 
+namespace {
+template <uint32_t kMetric, bool kTerms>
+void launch_sim_as(const DevIndex& X, const SimArgs& A, hipStream_t s) {
+    if (X.csize == 4) hipLaunchKernelGGL((k_sim<true, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, X, A);
+    else hipLaunchKernelGGL((k_sim<false, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, X, A);
+}
+template <uint32_t kMetric>
+void launch_sim_by_terms(const DevIndex& X, const SimArgs& A, hipStream_t s) {
+    if (A.terms) launch_sim_as<kMetric, true>(X, A, s);
+    else launch_sim_as<kMetric, false>(X, A, s);
+}
+}  // namespace
+
+hipError_t launch_similarity_m(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term, const uint8_t* raw,
+                               const uint64_t* off, uint32_t n, uint32_t stride, const uint32_t* counts,
+                               const uint32_t* keys, uint32_t metric, float* sim, uint32_t* terms, hipStream_t s) {
+    if (metric >= kSimMetrics) return hipErrorInvalidValue;
+    if (!n || !stride) return hipSuccess;
+    if (!X.kt_off && !key_term) return hipErrorInvalidValue;
+    SimArgs A{raw, off, counts, keys, sim, terms, key_term, n, stride, {}};
+    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
+    if (metric == kSimOsa) launch_sim_by_terms<kSimOsa>(X, A, s);
+    else if (metric == kSimPartial) launch_sim_by_terms<kSimPartial>(X, A, s);
+    else launch_sim_by_terms<kSimLevenshtein>(X, A, s);
+    return hipGetLastError();
+}
+
 hipError_t launch_rerank(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
                          float min_sim, hipStream_t s) {
+    return launch_rerank_m(n, stride, counts, keys, scores, sim, nullptr, min_sim, s);
+}
+
+hipError_t launch_rerank_m(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
+                           uint32_t* terms, float min_sim, hipStream_t s) {
     if (!n) return hipSuccess;
     if (stride > kRerankMaxStride) return hipErrorInvalidValue;
     const uint32_t n2 = rerank_pow2(stride);  // every count's sort fits: counts are read as at most the stride
     const uint32_t threads = n2 / 2 < 64 ? 64 : (n2 / 2 > kRerankThreads ? kRerankThreads : n2 / 2);
     static_assert(kRerankPer * kRerankThreads == kRerankMaxStride, "a thread moves at most kRerankPer records");
-    hipLaunchKernelGGL(k_rerank, dim3(n), dim3(threads), sizeof(uint64_t) * n2, s, stride, counts, keys, scores, sim,
-                       min_sim);
+    if (terms)
+        hipLaunchKernelGGL(k_rerank<true>, dim3(n), dim3(threads), sizeof(uint64_t) * n2, s, stride, counts, keys, scores,
+                           sim, min_sim, terms);
+    else
+        hipLaunchKernelGGL(k_rerank<false>, dim3(n), dim3(threads), sizeof(uint64_t) * n2, s, stride, counts, keys, scores,
+                           sim, min_sim, terms);
     return hipGetLastError();
 }
 

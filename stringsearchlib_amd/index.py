@@ -26,6 +26,23 @@ NGS_ERR_QUERY_BUFFER = 0x10002
 NGS_ERR_RERANK_LIMIT = 0x10003
 
 
+# the similarity's metrics (NGS_SIM_* of include/ngram_search.h) and "no term was compared"
+METRICS = {"levenshtein": 0, "osa": 1, "partial": 2}
+NO_TERM = 0xFFFFFFFF
+
+
+def _metric(metric) -> int:
+    """"levenshtein" | "osa" | "partial" or the integer -> NGS_SIM_*."""
+    if isinstance(metric, str):
+        if metric not in METRICS:
+            raise ValueError(f"unknown metric {metric!r}: one of {sorted(METRICS)}")
+        return METRICS[metric]
+    m = int(metric)
+    if m not in METRICS.values():
+        raise ValueError(f"unknown metric {metric!r}: one of {sorted(METRICS.values())}")
+    return m
+
+
 def _check(what: str) -> None:
     """Raise if the last call on this thread failed (ngsLastError): the reference's entry points
     answer 0 on failure, which would otherwise read as "no results"."""
@@ -127,7 +144,7 @@ class StringIndex:
     _string = staticmethod(C.string_at)
     _RES = C.POINTER(C.POINTER(C.c_char))
     _fn = {"search": "search", "score": "score", "release": "release", "scoreBatch": "scoreBatch", "key": "ngsKey",
-           "scoreBatchSim": "scoreBatchSim"}
+           "scoreBatchSim": "scoreBatchSim", "scoreBatchSimM": "scoreBatchSimM"}
 
     def _queries(self, queries):
         return (C.c_char_p * max(1, len(queries)))(*[_b(q) for q in queries])
@@ -195,10 +212,17 @@ class StringIndex:
             getattr(L, f["release"])(self.handle, res, sc)
         return out
 
-    def score_batch_sim(self, queries, threshold: float = 0.0, limit: int = 100, min_similarity: float = 0.0):
+    def score_batch_sim(self, queries, threshold: float = 0.0, limit: int = 100, min_similarity: float = 0.0,
+                        metric=None, with_terms: bool = False):
         """scoreBatchSim: score_batch re-ranked by the edit-distance similarity (include/ngram_search.h):
         one list of (key, score, sim) per query, records with sim < min_similarity dropped, the rest in
-        order of (sim descending, the search's order ascending). min(limit, keys) must be at most 4,096."""
+        order of (sim descending, the search's order ascending). min(limit, keys) must be at most 4,096.
+        metric: "levenshtein" (the default), "osa" or "partial", or NGS_SIM_*'s integer (scoreBatchSimM).
+        with_terms: every result is (key, score, sim, term), term the matched term's string as `term`
+        returns it, None where no term was compared."""
+        if metric is not None or with_terms:
+            return self._score_batch_sim_m(queries, threshold, limit, min_similarity,
+                                           _metric("levenshtein" if metric is None else metric), with_terms)
         L, f = _native.lib(), self._fn
         nq = len(queries)
         qs = self._queries(queries)
@@ -222,6 +246,62 @@ class StringIndex:
         if sv:
             getattr(L, f["release"])(self.handle, None, sv)
         return out
+
+    def _score_batch_sim_m(self, queries, threshold, limit, min_similarity, metric: int, with_terms: bool):
+        L, f = _native.lib(), self._fn
+        nq = len(queries)
+        qs = self._queries(queries)
+        counts = (C.c_uint32 * max(1, nq))()
+        res = self._RES()
+        sc = C.POINTER(C.c_float)()
+        sv = C.POINTER(C.c_float)()
+        tv = C.POINTER(C.c_uint32)()
+        L.ngsLastError(1)
+        total = getattr(L, f["scoreBatchSimM"])(self.handle, qs, nq, threshold, limit, metric, min_similarity, counts,
+                                                C.byref(res), C.byref(sc), C.byref(sv),
+                                                C.byref(tv) if with_terms else None)
+        if not total:
+            _check(f["scoreBatchSimM"])
+        names: dict = {}  # term id -> string: one ngsTerm call per distinct term
+
+        def name(t):
+            if t == NO_TERM:
+                return None
+            if t not in names:
+                names[t] = self.term(t)
+            return names[t]
+
+        out, o = [], 0
+        for i in range(nq):
+            c = counts[i]
+            if with_terms:
+                out.append([(self._string(res[o + j]), sc[o + j], sv[o + j], name(tv[o + j])) for j in range(c)])
+            else:
+                out.append([(self._string(res[o + j]), sc[o + j], sv[o + j]) for j in range(c)])
+            o += c
+        assert o == total
+        if res:
+            getattr(L, f["release"])(self.handle, res, sc)
+        if sv:
+            getattr(L, f["release"])(self.handle, None, sv)
+        if tv:
+            L.ngsReleaseTerms(tv)
+        return out
+
+    def term(self, term_id: int):
+        """ngsTerm: the normalised term `term_id` (0 .. size() - 1) as the index holds it, in the type
+        this class returns keys in. One small device copy per call: for showing results, not for export."""
+        L = _native.lib()
+        n = L.ngsTerm(self.handle, term_id, None, 0)
+        if n < 0:
+            raise IndexError(term_id) if n == -3 else RuntimeError(f"ngsTerm failed: {n}")
+        buf = (C.c_uint8 * max(1, n * self._CS))()
+        got = L.ngsTerm(self.handle, term_id, buf, n * self._CS)
+        if got != n:
+            raise RuntimeError(f"ngsTerm failed: {got}")
+        return self._term_string(bytes(buf[:n * self._CS]))
+
+    _term_string = staticmethod(bytes)
 
     def dispose(self) -> None:
         if self.handle:
@@ -280,18 +360,36 @@ class StringIndex:
 
 
     def similarity_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
-                          d_sim: int, stream: int = 0) -> None:
+                          d_sim: int, stream: int = 0, metric=None, d_terms: int = 0) -> None:
         """ngsSimilarityDevice on raw device pointers: d_sim[i * stride + r] = the edit-distance similarity of
-        query i and key d_keys[i * stride + r], r < d_counts[i]; queued on `stream`, nothing waits."""
+        query i and key d_keys[i * stride + r], r < d_counts[i]; queued on `stream`, nothing waits.
+        With a metric or d_terms (the matched term ids, in d_sim's layout): ngsSimilarityDeviceM."""
+        if metric is not None or d_terms:
+            rc = _native.lib().ngsSimilarityDeviceM(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys,
+                                                    _metric("levenshtein" if metric is None else metric), d_sim,
+                                                    d_terms or None, stream or None)
+            if rc:
+                raise RuntimeError(f"ngsSimilarityDeviceM failed: {rc}")
+            return
         rc = _native.lib().ngsSimilarityDevice(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_sim,
                                                stream or None)
         if rc:
             raise RuntimeError(f"ngsSimilarityDevice failed: {rc}")
 
     def rerank_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
-                      d_scores: int, d_sim: int, min_similarity: float = 0.0, stream: int = 0) -> None:
+                      d_scores: int, d_sim: int, min_similarity: float = 0.0, stream: int = 0, metric=None,
+                      d_terms: int = 0) -> None:
         """ngsRerankDevice on raw device pointers: the similarity, then every query's records filtered by
-        min_similarity and ordered by (sim descending, position ascending), in place; queued on `stream`."""
+        min_similarity and ordered by (sim descending, position ascending), in place; queued on `stream`.
+        With a metric or d_terms (the matched term ids, permuted with the records): ngsRerankDeviceM."""
+        if metric is not None or d_terms:
+            rc = _native.lib().ngsRerankDeviceM(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores,
+                                                d_sim, d_terms or None,
+                                                _metric("levenshtein" if metric is None else metric), min_similarity,
+                                                stream or None)
+            if rc:
+                raise RuntimeError(f"ngsRerankDeviceM failed: {rc}")
+            return
         rc = _native.lib().ngsRerankDevice(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores,
                                            d_sim, min_similarity, stream or None)
         if rc:
@@ -317,18 +415,23 @@ class StringIndex:
         assert sum(map(len, out)) == total
         return out
 
-    def dedup(self, threshold: float, limit: int = 10, min_similarity: float | None = None, batch_keys: int = 0):
+    def dedup(self, threshold: float, limit: int = 10, min_similarity: float | None = None, batch_keys: int = 0,
+              metric=None):
         """dedupKeys: labels[k] = the smallest key id of key k's cluster, the clusters being the
         connected components of the self-join at (threshold, limit); with min_similarity, of its records
-        whose edit-distance similarity is at least that. limit in 1..4,096."""
+        whose edit-distance similarity is at least that. limit in 1..4,096. metric: the similarity's
+        (dedupKeysM); "partial" is directional, and an edge is made if either key's row keeps it."""
         L = _native.lib()
         nk = self.num_keys()
         labels = (C.c_uint32 * max(1, nk))()
         L.ngsLastError(1)
-        clusters = L.dedupKeys(self.handle, threshold, limit, -1.0 if min_similarity is None else min_similarity,
-                               batch_keys, labels)
+        ms = -1.0 if min_similarity is None else min_similarity
+        if metric is None:
+            clusters = L.dedupKeys(self.handle, threshold, limit, ms, batch_keys, labels)
+        else:
+            clusters = L.dedupKeysM(self.handle, threshold, limit, _metric(metric), ms, batch_keys, labels)
         if not clusters:
-            _check("dedupKeys")
+            _check("dedupKeys" if metric is None else "dedupKeysM")
         out = list(labels[:nk])
         assert clusters == sum(1 for k, v in enumerate(out) if k == v)
         return out
@@ -421,7 +524,7 @@ class WideStringIndex(StringIndex):
     _CS = 4
     _RES = C.POINTER(_U32P)
     _fn = {"search": "searchW", "score": "scoreW", "release": "releaseW", "scoreBatch": "scoreBatchW",
-           "key": "ngsKeyW", "scoreBatchSim": "scoreBatchSimW"}
+           "key": "ngsKeyW", "scoreBatchSim": "scoreBatchSimW", "scoreBatchSimM": "scoreBatchSimMW"}
 
     def __init__(self, words, row_size: int = 1, weights=None, device: int | None = None, gram_size: int = 2,
                  devices=None):
@@ -443,6 +546,7 @@ class WideStringIndex(StringIndex):
         return C.cast(_u32(query), _U32P)
 
     _string = staticmethod(_wstring)
+    _term_string = staticmethod(lambda b: "".join(map(chr, memoryview(b).cast("I"))))
 
     def _queries(self, queries):
         arrs = [_u32(q) for q in queries]
@@ -489,7 +593,7 @@ class Utf8StringIndex(WideStringIndex):
     _INDEX = "indexU8"
     _RES = C.POINTER(C.POINTER(C.c_char))
     _fn = {"search": "searchU8", "score": "scoreU8", "release": "release", "scoreBatch": "scoreBatchU8",
-           "key": "ngsKeyU8", "scoreBatchSim": "scoreBatchSimU8"}
+           "key": "ngsKeyU8", "scoreBatchSim": "scoreBatchSimU8", "scoreBatchSimM": "scoreBatchSimMU8"}
 
     @staticmethod
     def _words(words):

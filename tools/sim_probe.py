@@ -8,9 +8,12 @@ alternately: host clock from before the call to the end of a stream synchronise,
 each, the median of --reps calls with the 10th / 90th percentiles as the spread. The stage's own
 time comes from HIP events around ngsRerankDevice (and around ngsSimilarityDevice alone) on the
 same stream. Records and term characters are counted on the host from the search's answer.
+--metric NAME (repeatable; "levenshtein", "osa" or "partial") times the same stage through
+ngsRerankDeviceM / ngsSimilarityDeviceM by that metric as well, alternating with the stage above
+within every repetition; --terms has those calls write the matched term ids too.
 Prints one JSON line.
 
-    python tools/sim_probe.py [--rows 200000] [--queries 4096] [--reps 30]
+    python tools/sim_probe.py [--rows 200000] [--queries 4096] [--reps 30] [--metric osa --metric partial] [--terms]
 """
 import argparse
 import json
@@ -51,6 +54,8 @@ def main():
     ap.add_argument("--threshold", type=float, default=0.3)
     ap.add_argument("--limit", type=int, default=100)
     ap.add_argument("--min-similarity", type=float, default=0.0)
+    ap.add_argument("--metric", action="append", default=[], choices=sorted(ssl.METRICS))
+    ap.add_argument("--terms", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sim_probe: no GPU")
@@ -66,6 +71,8 @@ def main():
     dk = torch.zeros(nq * stride, dtype=torch.int32, device=dev)
     ds = torch.zeros(nq * stride, dtype=torch.float32, device=dev)
     dv = torch.zeros(nq * stride, dtype=torch.float32, device=dev)
+    dt = torch.zeros(nq * stride, dtype=torch.int32, device=dev)
+    d_terms = dt.data_ptr() if a.terms else 0
     st = torch.cuda.Stream()
     torch.cuda.synchronize()
     args = (raw.data_ptr(), off.data_ptr(), nq)
@@ -77,20 +84,28 @@ def main():
         st.synchronize()
         return (time.perf_counter() - t) * 1e3
 
-    def search_rerank():
+    def search_rerank(metric=None):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t = time.perf_counter()
         ix.search_device(*args, a.threshold, a.limit, stride, *outs, st.cuda_stream)
         e0.record(st)
-        ix.rerank_device(*args, stride, *outs, dv.data_ptr(), a.min_similarity, st.cuda_stream)
+        if metric is None:
+            ix.rerank_device(*args, stride, *outs, dv.data_ptr(), a.min_similarity, st.cuda_stream)
+        else:
+            ix.rerank_device(*args, stride, *outs, dv.data_ptr(), a.min_similarity, st.cuda_stream, metric=metric,
+                             d_terms=d_terms)
         e1.record(st)
         st.synchronize()
         return (time.perf_counter() - t) * 1e3, e0.elapsed_time(e1)
 
-    def similarity_alone():
+    def similarity_alone(metric=None):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(st)
-        ix.similarity_device(*args, stride, dn.data_ptr(), dk.data_ptr(), dv.data_ptr(), st.cuda_stream)
+        if metric is None:
+            ix.similarity_device(*args, stride, dn.data_ptr(), dk.data_ptr(), dv.data_ptr(), st.cuda_stream)
+        else:
+            ix.similarity_device(*args, stride, dn.data_ptr(), dk.data_ptr(), dv.data_ptr(), st.cuda_stream,
+                                 metric=metric, d_terms=d_terms)
         e1.record(st)
         st.synchronize()
         return e0.elapsed_time(e1)
@@ -98,7 +113,10 @@ def main():
     for _ in range(a.warmup):
         search()
         search_rerank()
+        for mt in a.metric:
+            search_rerank(mt)
     t_search, t_both, t_stage, t_sim = [], [], [], []
+    m_stage, m_sim = {mt: [] for mt in a.metric}, {mt: [] for mt in a.metric}
     for _ in range(a.reps):
         t_search.append(search())
         # the search's answer as the stage finds it: records, term characters, bytes its gathers touch
@@ -113,10 +131,15 @@ def main():
             records, term_chars = int(counts.sum()), int(lens.sum())
             # key id (streamed), then three dependent random reads (key -> term, its two offsets, its bytes)
             gather_bytes = int(4 * records + 2 * SECTOR * records + (SECTOR * ((lens + 3 + SECTOR - 1) // SECTOR)).sum())
-            t_sim.extend(similarity_alone() for _ in range(a.reps))
+            for _ in range(a.reps):  # (the search's answer is still in place: nothing re-ranked it yet)
+                t_sim.append(similarity_alone())
+                for mt in a.metric:
+                    m_sim[mt].append(similarity_alone(mt))
         both, stage = search_rerank()
         t_both.append(both)
         t_stage.append(stage)
+        for mt in a.metric:
+            m_stage[mt].append(search_rerank(mt)[1])
     kept = int(dn.cpu().numpy().astype(np.int64).sum())
     m = [len(sim_ref.normalise(q)) for q in queries]
     long_q = np.array([x > 64 for x in m])
@@ -129,6 +152,9 @@ def main():
         "records": records, "records_kept": kept, "term_chars": term_chars,
         "records_per_s": round(records / (mg * 1e-3)), "term_chars_per_s": round(term_chars / (mg * 1e-3)),
         "long_path_share": round(float(counts[long_q].sum()) / max(records, 1), 6),
+        "terms": a.terms,
+        "metrics": {mt: {"rerank_stage_ms": spread(m_stage[mt]), "similarity_kernel_ms": spread(m_sim[mt]),
+                         "stage_ratio": round(statistics.median(m_stage[mt]) / mg, 4)} for mt in a.metric},
         "gather_bytes": gather_bytes, "gather_GBps_similarity": round(gather_bytes / (mv * 1e-3) / 1e9, 2),
         "version": _native.lib().ngsVersion().decode()}))
     ix.dispose()
