@@ -57,6 +57,106 @@ def source_hash() -> str:
     return h.hexdigest()[:16]
 
 
+# ---- the exports' signatures (include/ngram_search.h) ----
+u32, u64, f32, cp, vp, ci = C.c_uint32, C.c_uint64, C.c_float, C.c_char_p, C.c_void_p, C.c_int
+P = C.POINTER
+PP = P(P(C.c_char))      # char**: narrow and UTF-8 results
+W = P(C.c_uint32)        # wchar_t*: 4 bytes on Linux, bound as uint32 units
+PW = P(W)
+PF, PT, PU = P(P(f32)), P(P(u32)), P(u32)
+# a call that exists per string width: suffix -> (a string, a results array); UTF-8 is char* on a wide index
+_WIDTHS = {"": (cp, PP), "W": (W, PW), "U8": (cp, PP)}
+STR, STRS, RES = "a string", "an array of strings", "the address of a results array"
+
+
+def _by_width(widths, rows):
+    """{name + suffix: (restype, argtypes)} for every suffix of `widths`, STR / STRS / RES filled in."""
+    out = {}
+    for w in widths:
+        s, r = _WIDTHS[w]
+        fill = {STR: s, STRS: P(s), RES: P(r)}
+        for name, (restype, argtypes) in rows.items():
+            out[name + w] = (restype, [fill.get(a, a) for a in argtypes])
+    return out
+
+
+_QUERY = {"search": (u32, [u32, STR, RES, f32, u32]),
+          "score": (u32, [u32, STR, RES, PF, f32, u32]),
+          "scoreBatch": (u32, [u32, STRS, u32, f32, u32, PU, RES, PF]),
+          "searchBatch": (u32, [u32, STRS, u32, f32, u32, PU, RES])}
+_SEARCH_DEVICE = (ci, [u32, vp, vp, u32, f32, u32, u32, vp, vp, vp, vp])
+# [(probe, {name: (restype, argtypes)})]: a group whose probe symbol the library lacks is skipped
+# (NGS_LIB experiment builds of older sources); probe None: every library has them
+EXPORTS = [
+    (None, {"indexN": (u32, [P(cp), u64, C.c_uint16, P(f32)]),
+            "release": (None, [u32, PP, P(f32)]),
+            "dispose": (None, [u32]),
+            "getSize": (u64, [u32]),
+            "getLibSize": (u64, [u32]),
+            "setValidChar": (None, [u32, cp, ci]),
+            **_by_width(("", "W"), _QUERY),
+            # wide / gram-size extensions
+            "indexG": (u32, [P(cp), u64, C.c_uint16, P(f32), C.c_uint16]),
+            "indexW": (u32, [P(W), u64, C.c_uint16, P(f32), C.c_uint16]),
+            "releaseW": (None, [u32, PW, P(f32)]),
+            "disposeW": (None, [u32]),
+            "getSizeW": (u64, [u32]),
+            "getLibSizeW": (u64, [u32]),
+            "ngsKeyW": (vp, [u32, u32]),
+            "ngsCharSize": (u32, [u32]),
+            "ngsGramSize": (u32, [u32]),
+            "ngsSetDevice": (ci, [ci]),
+            "ngsSetDevices": (ci, [P(ci), ci]),
+            "ngsReplicaCount": (ci, [u32]),
+            "ngsDeviceCount": (ci, []),
+            "ngsNumKeys": (u32, [u32]),
+            "ngsKey": (vp, [u32, u32]),
+            "ngsSearchDevice": _SEARCH_DEVICE,
+            "ngsSetTiming": (ci, [u32, ci]),
+            "ngsLastStats": (ci, [u32, P(NgsStats)]),
+            "ngsIndexDigest": (ci, [u32, P(u64), ci]),
+            "ngsVersion": (cp, []),
+            "ngsSaveIndex": (ci, [u32, cp]),
+            "ngsLoadIndex": (u32, [cp]),
+            "ngsHostPhases": (ci, [P(u64), ci, ci]),
+            "ngsPhaseStats": (ci, [P(u64), ci, ci])}),
+    # UTF-8 on wide indexes: strings in and out are char*, the index underneath is the wide one
+    ("indexU8", {"indexU8": (u32, [P(cp), u64, C.c_uint16, P(f32), C.c_uint16]),
+                 **_by_width(("U8",), _QUERY),
+                 "ngsKeyU8": (vp, [u32, u32]),
+                 "ngsUtf8Decode": (ci, [vp, vp, u32, vp, u64, vp, vp]),
+                 "ngsSearchDeviceU8": _SEARCH_DEVICE}),
+    ("ngsSearchDeviceAsync", {"ngsSearchDeviceAsync": (ci, _SEARCH_DEVICE[1] + [P(u64)]),
+                              "ngsSearchDeviceWait": (ci, [u32, u64])}),
+    ("ngsServe", {"ngsServe": (ci, [u32, ci])}),
+    ("ngsPackResults", {"ngsPackResults": (ci, [vp, vp, vp, u32, u32, vp, vp, vp])}),
+    # the similarity stage
+    ("ngsSimilarityDevice", {"ngsSimilarityDevice": (ci, [u32, vp, vp, u32, u32, vp, vp, vp, vp]),
+                             "ngsRerankDevice": (ci, [u32, vp, vp, u32, u32, vp, vp, vp, vp, f32, vp]),
+                             **_by_width(("", "W", "U8"), {
+                                 "scoreBatchSim": (u32, [u32, STRS, u32, f32, u32, f32, PU, RES, PF, PF])})}),
+    # ... by metric, with the matched term
+    ("ngsSimilarityDeviceM", {"ngsSimilarityDeviceM": (ci, [u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]),
+                              "ngsRerankDeviceM": (ci, [u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, f32, vp]),
+                              **_by_width(("", "W", "U8"), {
+                                  "scoreBatchSimM": (u32, [u32, STRS, u32, f32, u32, u32, f32, PU, RES, PF, PF, PT])}),
+                              "ngsReleaseTerms": (None, [PU]),
+                              "dedupKeysM": (u32, [u32, f32, u32, u32, f32, u32, PU]),
+                              "ngsTerm": (C.c_int64, [u32, u32, vp, u64])}),
+    # the self-join
+    ("ngsSelfJoinDevice", {"ngsKeyQueryBytes": (u64, [u32, u32, u32]),
+                           "ngsKeyQueriesDevice": (ci, [u32, u32, u32, vp, u64, vp, vp]),
+                           "ngsDropSelfDevice": (ci, [vp, vp, vp, u32, u32, u32, u32, vp]),
+                           "ngsSelfJoinDevice": (ci, [u32, u32, u32, f32, u32, u32, vp, vp, vp, vp]),
+                           "ngsClusterDevice": (ci, [vp, vp, u32, u32, u32, vp, u32, u32, vp]),
+                           "selfJoin": (u32, [u32, u32, u32, f32, u32, u32, PU, PU, P(f32)]),
+                           "dedupKeys": (u32, [u32, f32, u32, f32, u32, PU])}),
+    ("ngsServeState", {"ngsServeState": (ci, [u32])}),
+    ("ngsLastError", {"ngsLastError": (ci, [ci])}),
+    ("ngsReplicaDigest", {"ngsReplicaDigest": (ci, [u32, ci, P(u64), ci])}),
+]
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -64,183 +164,11 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C {CSRC}` (HIP, gfx950)")
     L = C.CDLL(LIB_PATH)
-    u32, u64, f32, cp = C.c_uint32, C.c_uint64, C.c_float, C.c_char_p
-    PP = C.POINTER(C.POINTER(C.c_char))
-    L.indexN.restype = u32
-    L.indexN.argtypes = [C.POINTER(cp), u64, C.c_uint16, C.POINTER(f32)]
-    L.search.restype = u32
-    L.search.argtypes = [u32, cp, C.POINTER(PP), f32, u32]
-    L.score.restype = u32
-    L.score.argtypes = [u32, cp, C.POINTER(PP), C.POINTER(C.POINTER(f32)), f32, u32]
-    L.release.restype = None
-    L.release.argtypes = [u32, PP, C.POINTER(f32)]
-    L.dispose.restype = None
-    L.dispose.argtypes = [u32]
-    L.getSize.restype = u64
-    L.getSize.argtypes = [u32]
-    L.getLibSize.restype = u64
-    L.getLibSize.argtypes = [u32]
-    L.setValidChar.restype = None
-    L.setValidChar.argtypes = [u32, cp, C.c_int]
-    L.scoreBatch.restype = u32
-    L.scoreBatch.argtypes = [u32, C.POINTER(cp), u32, f32, u32, C.POINTER(u32), C.POINTER(PP),
-                             C.POINTER(C.POINTER(f32))]
-    L.searchBatch.restype = u32
-    L.searchBatch.argtypes = [u32, C.POINTER(cp), u32, f32, u32, C.POINTER(u32), C.POINTER(PP)]
-    # wide / gram-size extensions: wchar_t is 4 bytes on Linux, bound as uint32 units
-    W = C.POINTER(C.c_uint32)
-    PW = C.POINTER(W)
-    L.indexG.restype = u32
-    L.indexG.argtypes = [C.POINTER(cp), u64, C.c_uint16, C.POINTER(f32), C.c_uint16]
-    L.indexW.restype = u32
-    L.indexW.argtypes = [C.POINTER(W), u64, C.c_uint16, C.POINTER(f32), C.c_uint16]
-    L.searchW.restype = u32
-    L.searchW.argtypes = [u32, W, C.POINTER(PW), f32, u32]
-    L.scoreW.restype = u32
-    L.scoreW.argtypes = [u32, W, C.POINTER(PW), C.POINTER(C.POINTER(f32)), f32, u32]
-    L.scoreBatchW.restype = u32
-    L.scoreBatchW.argtypes = [u32, C.POINTER(W), u32, f32, u32, C.POINTER(u32), C.POINTER(PW),
-                              C.POINTER(C.POINTER(f32))]
-    L.searchBatchW.restype = u32
-    L.searchBatchW.argtypes = [u32, C.POINTER(W), u32, f32, u32, C.POINTER(u32), C.POINTER(PW)]
-    L.releaseW.restype = None
-    L.releaseW.argtypes = [u32, PW, C.POINTER(f32)]
-    L.disposeW.restype = None
-    L.disposeW.argtypes = [u32]
-    L.getSizeW.restype = u64
-    L.getSizeW.argtypes = [u32]
-    L.getLibSizeW.restype = u64
-    L.getLibSizeW.argtypes = [u32]
-    L.ngsKeyW.restype = C.c_void_p
-    L.ngsKeyW.argtypes = [u32, u32]
-    # UTF-8 on wide indexes: strings in and out are char*, the index underneath is the wide one
-    if hasattr(L, "indexU8"):  # (experiment builds of older sources lack them)
-        L.indexU8.restype = u32
-        L.indexU8.argtypes = [C.POINTER(cp), u64, C.c_uint16, C.POINTER(f32), C.c_uint16]
-        L.searchU8.restype = u32
-        L.searchU8.argtypes = [u32, cp, C.POINTER(PP), f32, u32]
-        L.scoreU8.restype = u32
-        L.scoreU8.argtypes = [u32, cp, C.POINTER(PP), C.POINTER(C.POINTER(f32)), f32, u32]
-        L.scoreBatchU8.restype = u32
-        L.scoreBatchU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, C.POINTER(u32), C.POINTER(PP),
-                                   C.POINTER(C.POINTER(f32))]
-        L.searchBatchU8.restype = u32
-        L.searchBatchU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, C.POINTER(u32), C.POINTER(PP)]
-        L.ngsKeyU8.restype = C.c_void_p
-        L.ngsKeyU8.argtypes = [u32, u32]
-        L.ngsUtf8Decode.restype = C.c_int
-        L.ngsUtf8Decode.argtypes = [C.c_void_p, C.c_void_p, u32, C.c_void_p, u64, C.c_void_p, C.c_void_p]
-        L.ngsSearchDeviceU8.restype = C.c_int
-        L.ngsSearchDeviceU8.argtypes = [u32, C.c_void_p, C.c_void_p, u32, f32, u32, u32, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-    L.ngsCharSize.restype = u32
-    L.ngsCharSize.argtypes = [u32]
-    L.ngsGramSize.restype = u32
-    L.ngsGramSize.argtypes = [u32]
-    L.ngsSetDevice.restype = C.c_int
-    L.ngsSetDevice.argtypes = [C.c_int]
-    L.ngsSetDevices.restype = C.c_int
-    L.ngsSetDevices.argtypes = [C.POINTER(C.c_int), C.c_int]
-    L.ngsReplicaCount.restype = C.c_int
-    L.ngsReplicaCount.argtypes = [u32]
-    L.ngsDeviceCount.restype = C.c_int
-    L.ngsDeviceCount.argtypes = []
-    L.ngsNumKeys.restype = u32
-    L.ngsNumKeys.argtypes = [u32]
-    L.ngsKey.restype = C.c_void_p
-    L.ngsKey.argtypes = [u32, u32]
-    L.ngsSearchDevice.restype = C.c_int
-    L.ngsSearchDevice.argtypes = [u32, C.c_void_p, C.c_void_p, u32, f32, u32, u32, C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.c_void_p]
-    if hasattr(L, "ngsSearchDeviceAsync"):  # (experiment builds of older sources lack it)
-        L.ngsSearchDeviceAsync.restype = C.c_int
-        L.ngsSearchDeviceAsync.argtypes = [u32, C.c_void_p, C.c_void_p, u32, f32, u32, u32, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
-        L.ngsSearchDeviceWait.restype = C.c_int
-        L.ngsSearchDeviceWait.argtypes = [u32, C.c_uint64]
-    if hasattr(L, "ngsServe"):
-        L.ngsServe.restype = C.c_int
-        L.ngsServe.argtypes = [u32, C.c_int]
-    if hasattr(L, "ngsPackResults"):
-        L.ngsPackResults.restype = C.c_int
-        L.ngsPackResults.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p]
-    if hasattr(L, "ngsSimilarityDevice"):  # (experiment builds of older sources lack the similarity stage)
-        L.ngsSimilarityDevice.restype = C.c_int
-        L.ngsSimilarityDevice.argtypes = [u32, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_void_p]
-        L.ngsRerankDevice.restype = C.c_int
-        L.ngsRerankDevice.argtypes = [u32, C.c_void_p, C.c_void_p, u32, u32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, f32, C.c_void_p]
-        PF = C.POINTER(C.POINTER(f32))
-        L.scoreBatchSim.restype = u32
-        L.scoreBatchSim.argtypes = [u32, C.POINTER(cp), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF, PF]
-        L.scoreBatchSimW.restype = u32
-        L.scoreBatchSimW.argtypes = [u32, C.POINTER(W), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PW), PF, PF]
-        L.scoreBatchSimU8.restype = u32
-        L.scoreBatchSimU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF, PF]
-    if hasattr(L, "ngsSimilarityDeviceM"):  # (experiment builds of older sources lack the metrics)
-        vp = C.c_void_p
-        PF, PT = C.POINTER(C.POINTER(f32)), C.POINTER(C.POINTER(u32))
-        L.ngsSimilarityDeviceM.restype = C.c_int
-        L.ngsSimilarityDeviceM.argtypes = [u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]
-        L.ngsRerankDeviceM.restype = C.c_int
-        L.ngsRerankDeviceM.argtypes = [u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, f32, vp]
-        L.scoreBatchSimM.restype = u32
-        L.scoreBatchSimM.argtypes = [u32, C.POINTER(cp), u32, f32, u32, u32, f32, C.POINTER(u32), C.POINTER(PP), PF,
-                                     PF, PT]
-        L.scoreBatchSimMW.restype = u32
-        L.scoreBatchSimMW.argtypes = [u32, C.POINTER(W), u32, f32, u32, u32, f32, C.POINTER(u32), C.POINTER(PW), PF,
-                                      PF, PT]
-        L.scoreBatchSimMU8.restype = u32
-        L.scoreBatchSimMU8.argtypes = [u32, C.POINTER(cp), u32, f32, u32, u32, f32, C.POINTER(u32), C.POINTER(PP),
-                                       PF, PF, PT]
-        L.ngsReleaseTerms.restype = None
-        L.ngsReleaseTerms.argtypes = [C.POINTER(u32)]
-        L.dedupKeysM.restype = u32
-        L.dedupKeysM.argtypes = [u32, f32, u32, u32, f32, u32, C.POINTER(u32)]
-        L.ngsTerm.restype = C.c_int64
-        L.ngsTerm.argtypes = [u32, u32, vp, u64]
-    if hasattr(L, "ngsSelfJoinDevice"):  # (experiment builds of older sources lack the self-join)
-        vp = C.c_void_p
-        L.ngsKeyQueryBytes.restype = u64
-        L.ngsKeyQueryBytes.argtypes = [u32, u32, u32]
-        L.ngsKeyQueriesDevice.restype = C.c_int
-        L.ngsKeyQueriesDevice.argtypes = [u32, u32, u32, vp, u64, vp, vp]
-        L.ngsDropSelfDevice.restype = C.c_int
-        L.ngsDropSelfDevice.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp]
-        L.ngsSelfJoinDevice.restype = C.c_int
-        L.ngsSelfJoinDevice.argtypes = [u32, u32, u32, f32, u32, u32, vp, vp, vp, vp]
-        L.ngsClusterDevice.restype = C.c_int
-        L.ngsClusterDevice.argtypes = [vp, vp, u32, u32, u32, vp, u32, u32, vp]
-        L.selfJoin.restype = u32
-        L.selfJoin.argtypes = [u32, u32, u32, f32, u32, u32, C.POINTER(u32), C.POINTER(u32), C.POINTER(f32)]
-        L.dedupKeys.restype = u32
-        L.dedupKeys.argtypes = [u32, f32, u32, f32, u32, C.POINTER(u32)]
-    if hasattr(L, "ngsServeState"):
-        L.ngsServeState.restype = C.c_int
-        L.ngsServeState.argtypes = [u32]
-    L.ngsSetTiming.restype = C.c_int
-    L.ngsSetTiming.argtypes = [u32, C.c_int]
-    if hasattr(L, "ngsLastError"):  # (experiment builds of older sources lack it)
-        L.ngsLastError.restype = C.c_int
-        L.ngsLastError.argtypes = [C.c_int]
-    L.ngsLastStats.restype = C.c_int
-    L.ngsLastStats.argtypes = [u32, C.POINTER(NgsStats)]
-    L.ngsIndexDigest.restype = C.c_int
-    L.ngsIndexDigest.argtypes = [u32, C.POINTER(u64), C.c_int]
-    if hasattr(L, "ngsReplicaDigest"):
-        L.ngsReplicaDigest.restype = C.c_int
-        L.ngsReplicaDigest.argtypes = [u32, C.c_int, C.POINTER(u64), C.c_int]
-    L.ngsVersion.restype = cp
-    L.ngsVersion.argtypes = []
-    L.ngsSaveIndex.restype = C.c_int
-    L.ngsSaveIndex.argtypes = [u32, cp]
-    L.ngsLoadIndex.restype = u32
-    L.ngsLoadIndex.argtypes = [cp]
-    L.ngsHostPhases.restype = C.c_int
-    L.ngsHostPhases.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
-    L.ngsPhaseStats.restype = C.c_int
-    L.ngsPhaseStats.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int]
+    for probe, group in EXPORTS:
+        if probe is None or hasattr(L, probe):
+            for name, (restype, argtypes) in group.items():
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
     version = L.ngsVersion().decode()
     want = source_hash()
     if not version.endswith(f"src={want}") and _variant:  # experiment builds (NGS_LIB) may predate the tree

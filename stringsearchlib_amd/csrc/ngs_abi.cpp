@@ -2381,6 +2381,24 @@ uint32_t new_library(Build&& build) {
     return handle;
 }
 
+// A search that answered kRetryQcap (k_prep flagged a batch that does not fit the context's
+// normalised-query buffer) runs again with the batch's byte count, read back on s; a second retry
+// is -5. Every other rc passes through.
+int rerun_outgrown(int rc, Library& L, Replica& R, Context& c, const uint8_t* d_raw, const uint64_t* d_off, uint32_t B,
+                   float thr, uint32_t Lm, uint32_t stride, uint32_t* d_n, uint32_t* d_k, float* d_s, hipStream_t s) {
+    if (rc != kRetryQcap) return rc;
+    uint64_t qbytes = 0;
+    rc = HIP_CHECK(hipMemcpyAsync(&qbytes, d_off + B, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) &&
+                 HIP_CHECK(hipStreamSynchronize(s))
+             ? device_search(L, R, c, d_raw, d_off, B, qbytes, thr, Lm, stride, d_n, d_k, d_s, s)
+             : -4;
+    if (rc == kRetryQcap) {
+        rc = -5;
+        t_last_error = kErrQueryBuffer;
+    }
+    return rc;
+}
+
 // ngsSearchDevice on replica R (the caller holds the shared lock and a BatchGuard, and R's device
 // is current): a context from R's pool, the search, the rerun when the batch outgrew the context's
 // normalised-query buffer.
@@ -2393,22 +2411,15 @@ int search_on_replica(Library& L, Replica& R, const uint8_t* d_raw, const uint64
     if (!c) return -4;
     // The batch's byte count sizes the normalised-query buffer. A context that has one already
     // launches without reading it back (a sync before any kernel); k_prep flags a batch that
-    // does not fit and the call reruns after the read-back.
+    // does not fit and the call reruns after the read-back (rerun_outgrown).
     int rc = 0;
-    auto read_bytes = [&](uint64_t& qb) -> bool {
-        return HIP_CHECK(hipMemcpyAsync(&qb, d_off + B, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) &&
-               HIP_CHECK(hipStreamSynchronize(s));
-    };
     uint64_t qbytes = 0;
-    if (B && !c->qcap && !read_bytes(qbytes)) rc = -4;
+    if (B && !c->qcap &&
+        !(HIP_CHECK(hipMemcpyAsync(&qbytes, d_off + B, sizeof(uint64_t), hipMemcpyDeviceToHost, s)) &&
+          HIP_CHECK(hipStreamSynchronize(s))))
+        rc = -4;
     if (!rc) rc = device_search(L, R, *c, d_raw, d_off, B, qbytes, thr, Lm, stride, d_n, d_k, d_s, s);
-    if (rc == kRetryQcap) {
-        rc = read_bytes(qbytes) ? device_search(L, R, *c, d_raw, d_off, B, qbytes, thr, Lm, stride, d_n, d_k, d_s, s) : -4;
-        if (rc == kRetryQcap) {
-            rc = -5;
-            t_last_error = kErrQueryBuffer;
-        }
-    }
+    rc = rerun_outgrown(rc, L, R, *c, d_raw, d_off, B, thr, Lm, stride, d_n, d_k, d_s, s);
     R.give_back(std::move(c));
     return rc;
 }
@@ -2445,12 +2456,11 @@ bool sim_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint3
     return d_off && d_n && !(n && stride && (!d_k || !d_v));
 }
 
-// Queues the similarity kernel (and, with `rerank`, the re-rank behind it) on s; nothing waits.
-// use_m: the M entry points' launchers (metric, and the matched terms in d_t when not null); the
-// entry points without a metric keep the launchers they had.
+// Queues the similarity kernel by `metric` (and, with `rerank`, the re-rank behind it) on s; nothing
+// waits. d_t: the matched terms, or null.
 int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
-                     uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, bool rerank, float min_sim, hipStream_t s,
-                     bool use_m = false, uint32_t metric = kSimLevenshtein, uint32_t* d_t = nullptr) {
+                     uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, uint32_t* d_t, uint32_t metric, bool rerank,
+                     float min_sim, hipStream_t s) {
     if (n == 0) return 0;
     bool ok = true;
     const uint32_t* key_term = sim_key_term(R, ok);
@@ -2460,39 +2470,57 @@ int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_
         std::lock_guard<std::mutex> g(L.valid_mu);
         std::memcpy(valid, L.valid, sizeof valid);
     }
-    if (use_m) {
-        if (!HIP_CHECK(launch_similarity_m(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, metric, d_v, d_t, s)))
-            return -4;
-        if (rerank && !HIP_CHECK(launch_rerank_m(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
-        return 0;
-    }
-    if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, d_v, s))) return -4;
-    if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, min_sim, s))) return -4;
+    if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, metric, d_v, d_t, s)))
+        return -4;
+    if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
     return 0;
 }
 
-// the entry points' common front: lock held by the caller; the replica on the current device
-int sim_entry(uint32_t handle, Library*& L, Replica*& R) {
+// The device entry points' front, in two halves (the caller holds the lock; each entry point puts
+// its own checks before, between and behind them). The library of `handle`: -1 none, -2 not built.
+int entry_library(uint32_t handle, Library*& L) {
     L = find_lib(handle);
     if (!L) return -1;
-    if (!L->host.indexed) return -2;
-    int cur = L->device;
+    return L->host.indexed ? 0 : -2;
+}
+// The replica on the caller's current device: -4 no device, -3 no replica there (the caller's
+// buffers and stream belong to that device).
+int entry_replica(Library& L, Replica*& R) {
+    int cur = L.device;
     if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
-    R = L->replica_at(cur);
-    return R ? 0 : -3;  // no replica on the caller's device: its buffers and stream belong there
+    R = L.replica_at(cur);
+    return R ? 0 : -3;
+}
+// the search calls' pointer and stride check, at the effective limit Lm
+bool search_args_ok(const uint64_t* d_off, uint32_t n, uint32_t Lm, uint32_t stride, const uint32_t* d_n,
+                    const uint32_t* d_k, const float* d_s) {
+    return d_off && d_n && !(n && Lm && (!d_k || !d_s || stride < Lm));
 }
 
-// Device buffers of one scoreBatchSim* call, freed when it returns.
-struct SimBuffers {
+// The stream and the device blocks of one host call of the later stages (scoreBatchSim*, selfJoin,
+// dedupKeys*, ngsSelfJoinDevice's gathered queries), freed when it returns.
+struct CallScratch {
     std::vector<void*> mem;
     hipStream_t stream = nullptr;
+    // the arrays every stage works on (begin); a stage's further ones are alloc calls of its own
+    uint8_t* d_raw = nullptr;
+    uint64_t* d_off = nullptr;
+    uint32_t *d_n = nullptr, *d_k = nullptr;
+    float* d_s = nullptr;
     template <class T>
     bool alloc(T** p, size_t n) {
         if (!dev_alloc(p, n)) return false;
         mem.push_back(*p);
         return true;
     }
-    ~SimBuffers() {
+    // the call's stream, and for batches of up to `rows` queries of `stride` records and
+    // `raw_bytes` query bytes: the bytes (with 16 bytes of slack behind them), the offsets, counts,
+    // key ids and scores
+    bool begin(size_t rows, size_t stride, size_t raw_bytes) {
+        return HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking)) && alloc(&d_raw, raw_bytes + 16) &&
+               alloc(&d_off, rows + 1) && alloc(&d_n, rows) && alloc(&d_k, rows * stride) && alloc(&d_s, rows * stride);
+    }
+    ~CallScratch() {
         if (stream) (void)hipStreamDestroy(stream);
         for (void* p : mem) (void)hipFree(p);
     }
@@ -2504,12 +2532,12 @@ constexpr size_t kSimChunkRecords = size_t(1) << 22;  // records (query x limit)
 // behind it on the same stream, then counts, key ids, scores and sims read back and the result
 // pointers built as marshal() builds every other call's. u8: UTF-8 queries on a wide index
 // (decoded on the host), the strings of the UTF-8 key table. The first replica answers.
-// use_m: scoreBatchSimM*: the similarity by `metric`, and with terms != null the matched term ids as
-// a fourth flat array (ngsReleaseTerms).
+// The similarity is by `metric`; with terms != null the matched term ids come back as a fourth flat
+// array (ngsReleaseTerms).
 template <typename CharT>
 uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, float thr, uint32_t limit, float min_sim,
-                   uint32_t* counts, CharT*** results, float** scores, float** sims, bool u8, bool use_m = false,
-                   uint32_t metric = kSimLevenshtein, uint32_t** terms = nullptr) {
+                   uint32_t* counts, CharT*** results, float** scores, float** sims, bool u8, uint32_t metric,
+                   uint32_t** terms) {
     if (counts) std::fill(counts, counts + nq, 0u);
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = find_lib(handle);
@@ -2541,16 +2569,25 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
         len = queries[i] ? str_len(queries[i]) : 0;
         return queries[i];
     };
+    // every query's characters and length, and the bytes of the largest chunk: the device buffers
+    // are made once, before the loop
     const uint32_t chunk = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, kSimChunkRecords / Lm));
-    SimBuffers M;
-    uint64_t* d_off = nullptr;
-    uint32_t *d_n = nullptr, *d_k = nullptr, *d_t = nullptr;
-    float *d_s = nullptr, *d_v = nullptr;
+    std::vector<const uint8_t*> q_ptr(nq);
+    std::vector<size_t> q_len(nq);
+    size_t raw_cap = 0;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        size_t bytes = 0;
+        for (uint32_t i = q0; i < q0 + std::min(chunk, nq - q0); ++i) {
+            q_ptr[i] = static_cast<const uint8_t*>(chars_of(i, q_len[i]));
+            bytes += q_len[i] * cs;
+        }
+        raw_cap = std::max(raw_cap, bytes);
+    }
+    CallScratch M;
+    uint32_t* d_t = nullptr;
+    float* d_v = nullptr;
     const size_t recs = (size_t)chunk * Lm;
-    if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_off, (size_t)chunk + 1) ||
-        !M.alloc(&d_n, chunk) || !M.alloc(&d_k, recs) || !M.alloc(&d_s, recs) || !M.alloc(&d_v, recs) ||
-        (terms && !M.alloc(&d_t, recs)))
-        return 0;
+    if (!M.begin(chunk, Lm, raw_cap) || !M.alloc(&d_v, recs) || (terms && !M.alloc(&d_t, recs))) return 0;
     std::vector<uint32_t> cnt(nq, 0), keys, h_n(chunk), h_k(recs);  // (counts stay zero unless the whole call succeeds)
     std::vector<uint32_t> tv, h_t(terms ? recs : 0);
     std::vector<float> sc, sv, h_s(recs), h_v(recs);
@@ -2561,30 +2598,28 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
         h_raw.clear();
         h_off[0] = 0;
         for (uint32_t i = 0; i < B; ++i) {
-            size_t len = 0;
-            const uint8_t* p = static_cast<const uint8_t*>(chars_of(q0 + i, len));
-            if (len) h_raw.insert(h_raw.end(), p, p + len * cs);
+            const uint8_t* p = q_ptr[q0 + i];
+            if (q_len[q0 + i]) h_raw.insert(h_raw.end(), p, p + q_len[q0 + i] * cs);
             h_off[i + 1] = h_raw.size();
         }
-        uint8_t* d_raw = nullptr;
-        if (!M.alloc(&d_raw, h_raw.size() + 8)) return 0;
-        if (!HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, M.stream)) ||
+        if (!HIP_CHECK(hipMemcpyAsync(M.d_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice,
+                                      M.stream)) ||
             (!h_raw.empty() &&
-             !HIP_CHECK(hipMemcpyAsync(d_raw, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, M.stream))))
+             !HIP_CHECK(hipMemcpyAsync(M.d_raw, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, M.stream))))
             return 0;
         // 2. the search, 3. the re-rank behind it
-        if (search_on_replica(*L, R, d_raw, d_off, B, thr, Lm, Lm, d_n, d_k, d_s, M.stream) != 0) {
+        if (search_on_replica(*L, R, M.d_raw, M.d_off, B, thr, Lm, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0) {
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (queue_similarity(*L, R, d_raw, d_off, B, Lm, d_n, d_k, d_s, d_v, true, min_sim, M.stream, use_m, metric,
-                             d_t) != 0)
+        if (queue_similarity(*L, R, M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, metric, true, min_sim,
+                             M.stream) != 0)
             return 0;
         // 4. everything back
         const size_t rb = (size_t)B * Lm;
-        if (!HIP_CHECK(hipMemcpyAsync(h_n.data(), d_n, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, M.stream)) ||
-            !HIP_CHECK(hipMemcpyAsync(h_k.data(), d_k, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream)) ||
-            !HIP_CHECK(hipMemcpyAsync(h_s.data(), d_s, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+        if (!HIP_CHECK(hipMemcpyAsync(h_n.data(), M.d_n, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_k.data(), M.d_k, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_s.data(), M.d_s, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_v.data(), d_v, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
             (terms &&
              !HIP_CHECK(hipMemcpyAsync(h_t.data(), d_t, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream))) ||
@@ -2620,6 +2655,13 @@ bool join_range_ok(const Library& L, uint32_t first, uint32_t n) {
 }
 uint64_t join_query_bytes(const Library& L, uint32_t first, uint32_t n) {
     return join_query_off(L.host.key_off.data(), first, n, L.host.csize);
+}
+// the most query bytes a batch takes when keys [first, first + nk) are gathered B at a time
+uint64_t join_max_query_bytes(const Library& L, uint32_t first, uint32_t nk, uint32_t B) {
+    uint64_t most = 0;
+    for (uint32_t k0 = first; k0 < first + nk; k0 += B)
+        most = std::max(most, join_query_bytes(L, k0, std::min(B, first + nk - k0)));
+    return most;
 }
 // the limit the join's search runs with: one more than the caller's, for the record that is found
 // and removed (limit 0: every key)
@@ -2667,27 +2709,21 @@ uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr,
     const uint32_t B = join_batch_keys(0, nk, Ls);
     // a batch's records come back packed ({key id, score bits} in row order behind the rows' offsets,
     // as ngsPackResults writes them): the bytes read back follow the records, not keys x stride
-    SimBuffers M;
-    uint8_t *d_raw = nullptr, *d_tmp = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t *d_n = nullptr, *d_k = nullptr, *d_pos = nullptr, *d_rec = nullptr;
-    float* d_s = nullptr;
-    uint64_t raw_cap = 0;
-    for (uint32_t k0 = first; k0 < first + nk; k0 += B)
-        raw_cap = std::max(raw_cap, join_query_bytes(*L, k0, std::min(B, first + nk - k0)));
+    CallScratch M;
+    uint8_t* d_tmp = nullptr;
+    uint32_t *d_pos = nullptr, *d_rec = nullptr;
     const size_t tmp_bytes = std::max<size_t>(pack_pairs_temp_bytes(B), 1 << 16);
-    if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_raw, raw_cap + 16) ||
-        !M.alloc(&d_off, (size_t)B + 1) || !M.alloc(&d_n, B) || !M.alloc(&d_k, (size_t)B * Ls) ||
-        !M.alloc(&d_s, (size_t)B * Ls) || !M.alloc(&d_pos, (size_t)B + 1) || !M.alloc(&d_rec, 2 * (size_t)B * Ls) ||
-        !M.alloc(&d_tmp, tmp_bytes))
+    if (!M.begin(B, Ls, join_max_query_bytes(*L, first, nk, B)) || !M.alloc(&d_pos, (size_t)B + 1) ||
+        !M.alloc(&d_rec, 2 * (size_t)B * Ls) || !M.alloc(&d_tmp, tmp_bytes))
         return fail(0);
     std::vector<uint32_t> h_pos((size_t)B + 1), h_rec;
     uint64_t total = 0;
     for (uint32_t done = 0; done < nk; done += B) {
         const uint32_t n = std::min(B, nk - done);
-        if (join_batch(*L, R, first + done, n, thr, limit, Ls, d_raw, d_off, d_n, d_k, d_s, M.stream, false) != 0)
+        if (join_batch(*L, R, first + done, n, thr, limit, Ls, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream,
+                       false) != 0)
             return fail(kErrInternal);
-        if (!HIP_CHECK(launch_pack_pairs(d_n, d_k, d_s, n, Ls, d_pos, d_rec, d_tmp, tmp_bytes, M.stream)) ||
+        if (!HIP_CHECK(launch_pack_pairs(M.d_n, M.d_k, M.d_s, n, Ls, d_pos, d_rec, d_tmp, tmp_bytes, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_pos.data(), d_pos, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost,
                                       M.stream)) ||
             !HIP_CHECK(hipStreamSynchronize(M.stream)))
@@ -2715,8 +2751,8 @@ uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr,
     return (uint32_t)total;
 }
 
-uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, uint32_t batch_keys, uint32_t* labels,
-                    bool use_m = false, uint32_t metric = kSimLevenshtein) {
+uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric, float min_sim, uint32_t batch_keys,
+                    uint32_t* labels) {
     if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim || metric >= kSimMetrics) {
         t_last_error = labels && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
         return 0;
@@ -2735,30 +2771,25 @@ uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, u
     const uint32_t Ls = join_search_limit(*L, limit);
     const uint32_t B = join_batch_keys(batch_keys, nk, Ls);
     const bool verify = min_sim > -1.0f;  // every similarity is >= -1: nothing to filter at or below it
-    SimBuffers M;
-    uint8_t* d_raw = nullptr;
-    uint64_t* d_off = nullptr;
-    uint32_t *d_n = nullptr, *d_k = nullptr, *d_lab = nullptr;
-    float *d_s = nullptr, *d_v = nullptr;
-    uint64_t raw_cap = 0;
-    for (uint32_t k0 = 0; k0 < nk; k0 += B) raw_cap = std::max(raw_cap, join_query_bytes(*L, k0, std::min(B, nk - k0)));
-    if (!HIP_CHECK(hipStreamCreateWithFlags(&M.stream, hipStreamNonBlocking)) || !M.alloc(&d_raw, raw_cap + 16) ||
-        !M.alloc(&d_off, (size_t)B + 1) || !M.alloc(&d_n, B) || !M.alloc(&d_k, (size_t)B * Ls) ||
-        !M.alloc(&d_s, (size_t)B * Ls) || !M.alloc(&d_lab, nk) || (verify && !M.alloc(&d_v, (size_t)B * Ls)))
+    CallScratch M;
+    uint32_t* d_lab = nullptr;
+    float* d_v = nullptr;
+    if (!M.begin(B, Ls, join_max_query_bytes(*L, 0, nk, B)) || !M.alloc(&d_lab, nk) ||
+        (verify && !M.alloc(&d_v, (size_t)B * Ls)))
         return 0;
     // the label array stays on the device across the batches: finished and read back once
     for (uint32_t done = 0; done < nk; done += B) {
         const uint32_t n = std::min(B, nk - done);
-        if (join_batch(*L, R, done, n, thr, limit, Ls, d_raw, d_off, d_n, d_k, d_s, M.stream, false) != 0) {
+        if (join_batch(*L, R, done, n, thr, limit, Ls, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream, false) != 0) {
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (verify && (queue_similarity(*L, R, d_raw, d_off, n, Ls, d_n, d_k, d_s, d_v, false, 0.0f, M.stream, use_m,
-                                        metric) != 0 ||
-                       !HIP_CHECK(launch_keep_similar(d_n, d_k, d_s, d_v, n, Ls, min_sim, M.stream))))
+        if (verify && (queue_similarity(*L, R, M.d_raw, M.d_off, n, Ls, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric,
+                                        false, 0.0f, M.stream) != 0 ||
+                       !HIP_CHECK(launch_keep_similar(M.d_n, M.d_k, M.d_s, d_v, n, Ls, min_sim, M.stream))))
             return 0;
         const uint32_t flags = (done == 0 ? kClusterInit : 0u) | (done + n == nk ? kClusterFinish : 0u);
-        if (!HIP_CHECK(launch_cluster(d_n, d_k, n, Ls, done, d_lab, nk, flags, M.stream))) return 0;
+        if (!HIP_CHECK(launch_cluster(M.d_n, M.d_k, n, Ls, done, d_lab, nk, flags, M.stream))) return 0;
     }
     if (!HIP_CHECK(hipMemcpyAsync(labels, d_lab, sizeof(uint32_t) * nk, hipMemcpyDeviceToHost, M.stream)) ||
         !HIP_CHECK(hipStreamSynchronize(M.stream)))
@@ -2767,6 +2798,28 @@ uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, float min_sim, u
     for (uint32_t k = 0; k < nk; ++k) clusters += labels[k] == k;
     return clusters;
 }
+
+// A scan's scratch: one grow-only buffer per (device, stream), 64 KiB at first, so that calls on
+// different streams never share one while their scans run; a buffer is replaced only after its
+// stream's earlier work has finished with it. The caller holds mu from get() until its kernels are
+// queued (the mutex orders the host-side bookkeeping only). Each user keeps an instance of its
+// own: two users' kernels may be queued on one stream at once.
+struct StreamScratch {
+    std::mutex mu;
+    std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> temp;
+    // {buffer, its bytes >= need}; {null, 0} after a HIP error
+    std::pair<void*, size_t> get(int dev, hipStream_t s, size_t need) {
+        auto& t = temp[{dev, s}];
+        if (need > t.second) {
+            if (t.first && !HIP_CHECK(hipStreamSynchronize(s))) return {nullptr, 0};
+            if (t.first) (void)hipFree(t.first);
+            t = {nullptr, 0};
+            if (!HIP_CHECK(hipMalloc(&t.first, std::max<size_t>(need, 1 << 16)))) return {nullptr, 0};
+            t.second = std::max<size_t>(need, 1 << 16);
+        }
+        return t;
+    }
+};
 }  // namespace
 }  // namespace ngs
 
@@ -2920,21 +2973,12 @@ NGS_API int ngsUtf8Decode(const uint8_t* dBytes, const uint64_t* dOffsets, uint3
                           uint64_t outCapBytes, uint64_t* dOutOffsets, void* stream) {
     if (!dOffsets || !dOutOffsets || (n && !dBytes) || (outCapBytes >= 4 && !dOut) || ((uintptr_t)dOut & 3u))
         return -3;
-    // the scan's scratch per (device, stream), kept as ngsPackResults keeps its own
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> temp;
+    static StreamScratch scratch;  // the scan's, kept as ngsPackResults keeps its own
     int dev = 0;
     if (!HIP_CHECK(hipGetDevice(&dev))) return -4;
-    std::lock_guard<std::mutex> g(mu);
-    auto& t = temp[{dev, (hipStream_t)stream}];
-    const size_t need = utf8_temp_bytes(n);
-    if (need > t.second) {
-        if (t.first && !HIP_CHECK(hipStreamSynchronize((hipStream_t)stream))) return -4;
-        if (t.first) (void)hipFree(t.first);
-        t = {nullptr, 0};
-        if (!HIP_CHECK(hipMalloc(&t.first, std::max<size_t>(need, 1 << 16)))) return -4;
-        t.second = std::max<size_t>(need, 1 << 16);
-    }
+    std::lock_guard<std::mutex> g(scratch.mu);
+    const auto t = scratch.get(dev, (hipStream_t)stream, utf8_temp_bytes(n));
+    if (!t.first) return -4;
     return HIP_CHECK(launch_utf8_decode(dBytes, dOffsets, n, reinterpret_cast<uint32_t*>(dOut), outCapBytes / 4,
                                         dOutOffsets, t.first, t.second, (hipStream_t)stream))
                ? 0
@@ -2945,16 +2989,13 @@ NGS_API int ngsSearchDeviceU8(uint32_t handle, const uint8_t* dQueryBytes, const
                               uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
                               uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream) {
     std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = find_lib(handle);
-    if (!L) return -1;
-    if (!L->host.indexed) return -2;
+    Library* L = nullptr;
+    Replica* Rp = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
     if (L->host.csize != sizeof(uint32_t)) return -3;
     const uint32_t Lm = effective_limit(*L, limit);
-    if (!dQueryOffsets || !dCounts || (nQueries && Lm && (!dKeys || !dScores || outStride < Lm))) return -3;
-    int cur = L->device;
-    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
-    Replica* Rp = L->replica_at(cur);
-    if (!Rp) return -3;
+    if (!search_args_ok(dQueryOffsets, nQueries, Lm, outStride, dCounts, dKeys, dScores)) return -3;
+    if (const int rc = entry_replica(*L, Rp)) return rc;
     Replica& R = *Rp;
     hipStream_t s = (hipStream_t)stream;
     BatchGuard bg(L);
@@ -2980,10 +3021,9 @@ NGS_API int ngsSearchDeviceU8(uint32_t handle, const uint8_t* dQueryBytes, const
                                      c->qcap / 4, c->d_off, c->d_u8temp, c->u8temp_bytes, s)))
         rc = device_search(*L, R, *c, c->d_raw, c->d_off, nQueries, qbytes, threshold, Lm, outStride, dCounts, dKeys,
                            dScores, s);
-    if (rc == kRetryQcap) {  // cannot happen: the buffer was sized for the batch
-        rc = -5;
-        t_last_error = kErrQueryBuffer;
-    }
+    // (cannot happen: the buffer was sized for the batch)
+    rc = rerun_outgrown(rc, *L, R, *c, c->d_raw, c->d_off, nQueries, threshold, Lm, outStride, dCounts, dKeys, dScores,
+                        s);
     R.give_back(std::move(c));
     return rc;
 }
@@ -3048,20 +3088,15 @@ NGS_API int ngsSearchDevice(uint32_t handle, const uint8_t* dQueryBytes, const u
                             uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride, uint32_t* dCounts,
                             uint32_t* dKeys, float* dScores, void* stream) {
     std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = find_lib(handle);
-    if (!L) return -1;
-    if (!L->host.indexed) return -2;
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
     const uint32_t Lm = effective_limit(*L, limit);
-    if (!dQueryOffsets || !dCounts || (nQueries && Lm && (!dKeys || !dScores || outStride < Lm))) return -3;
-    // the replica on the caller's current device (the buffers' device)
-    int cur = L->device;
-    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
-    Replica* Rp = L->replica_at(cur);
-    if (!Rp) return -3;  // no replica on the caller's device: its buffers and stream belong there
-    Replica& R = *Rp;
+    if (!search_args_ok(dQueryOffsets, nQueries, Lm, outStride, dCounts, dKeys, dScores)) return -3;
+    if (const int rc = entry_replica(*L, R)) return rc;
     hipStream_t s = (hipStream_t)stream;
     BatchGuard bg(L);
-    return search_on_replica(*L, R, dQueryBytes, dQueryOffsets, nQueries, threshold, Lm, outStride, dCounts, dKeys,
+    return search_on_replica(*L, *R, dQueryBytes, dQueryOffsets, nQueries, threshold, Lm, outStride, dCounts, dKeys,
                              dScores, s);
 }
 
@@ -3073,15 +3108,12 @@ NGS_API int ngsSearchDeviceAsync(uint32_t handle, const uint8_t* dQueryBytes, co
                                  uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
                                  uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream, uint64_t* ticket) {
     std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = find_lib(handle);
-    if (!L) return -1;
-    if (!L->host.indexed) return -2;
+    Library* L = nullptr;
+    Replica* Rp = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
     const uint32_t Lm = effective_limit(*L, limit);
-    if (!ticket || !dQueryOffsets || !dCounts || (nQueries && Lm && (!dKeys || !dScores || outStride < Lm))) return -3;
-    int cur = L->device;
-    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
-    Replica* Rp = L->replica_at(cur);
-    if (!Rp) return -3;
+    if (!ticket || !search_args_ok(dQueryOffsets, nQueries, Lm, outStride, dCounts, dKeys, dScores)) return -3;
+    if (const int rc = entry_replica(*L, Rp)) return rc;
     hipStream_t s = (hipStream_t)stream;
     BatchGuard bg(L);  // the server stops here; the pending call keeps it stopped until its Wait
     // the batch mark the pending call holds until its Wait; released here on any early return
@@ -3158,18 +3190,7 @@ NGS_API int ngsSearchDeviceWait(uint32_t handle, uint64_t ticket) {
         return -4;
     }
     int rc = pd.rc ? pd.rc : finish_search(*L, R, c, pd.B, pd.P, pd.doff, pd.dn, pd.dk, pd.ds, c.stream);
-    if (rc == kRetryQcap) {  // the batch outgrew the context's query buffer: rerun with its size
-        uint64_t qbytes = 0;
-        rc = HIP_CHECK(hipMemcpyAsync(&qbytes, pd.doff + pd.B, sizeof(uint64_t), hipMemcpyDeviceToHost, c.stream)) &&
-                     HIP_CHECK(hipStreamSynchronize(c.stream))
-                 ? device_search(*L, R, c, pd.dq, pd.doff, pd.B, qbytes, pd.thr, pd.Lm, pd.stride, pd.dn, pd.dk,
-                                 pd.ds, c.stream)
-                 : -4;
-        if (rc == kRetryQcap) {
-            rc = -5;
-            t_last_error = kErrQueryBuffer;
-        }
-    }
+    rc = rerun_outgrown(rc, *L, R, c, pd.dq, pd.doff, pd.B, pd.thr, pd.Lm, pd.stride, pd.dn, pd.dk, pd.ds, c.stream);
     R.give_back(std::move(pd.c));
     return rc;
 }
@@ -3200,73 +3221,52 @@ NGS_API int ngsPackResults(const uint32_t* dCounts, const uint32_t* dKeys, const
                            uint32_t stride, uint32_t* dOffsets, uint32_t* dRecords, void* stream) {
     if (!dCounts || !dOffsets || (n && (!dKeys || !dScores || !dRecords || !stride))) return -3;
     if ((uint64_t)n * stride > 0xFFFFFFFFull) return -3;  // the offsets are 32-bit
-    // the scan's scratch: one grow-only buffer per (device, stream), so that calls on different
-    // streams never share one while their scans run; a buffer is replaced only after its stream's
-    // earlier work has finished with it. (The mutex orders the host-side bookkeeping only.)
-    static std::mutex mu;
-    static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> temp;
+    static StreamScratch scratch;  // the scan's
     int dev = 0;
     if (!HIP_CHECK(hipGetDevice(&dev))) return -4;
-    std::lock_guard<std::mutex> g(mu);
-    auto& t = temp[{dev, (hipStream_t)stream}];
-    const size_t need = pack_pairs_temp_bytes(n);
-    if (need > t.second) {
-        if (t.first && !HIP_CHECK(hipStreamSynchronize((hipStream_t)stream))) return -4;
-        if (t.first) (void)hipFree(t.first);
-        t = {nullptr, 0};
-        if (!HIP_CHECK(hipMalloc(&t.first, std::max<size_t>(need, 1 << 16)))) return -4;
-        t.second = std::max<size_t>(need, 1 << 16);
-    }
+    std::lock_guard<std::mutex> g(scratch.mu);
+    const auto t = scratch.get(dev, (hipStream_t)stream, pack_pairs_temp_bytes(n));
+    if (!t.first) return -4;
     return HIP_CHECK(launch_pack_pairs(dCounts, dKeys, dScores, n, stride, dOffsets, dRecords, t.first, t.second,
                                        (hipStream_t)stream))
                ? 0
                : -4;
 }
 
+// The entry points without a metric are the M forms at kSimLevenshtein without terms.
 NGS_API int ngsSimilarityDevice(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
                                 uint32_t nQueries, uint32_t stride, const uint32_t* dCounts, const uint32_t* dKeys,
                                 float* dSim, void* stream) {
-    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim)) return -3;
-    std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = nullptr;
-    Replica* R = nullptr;
-    if (const int rc = sim_entry(handle, L, R)) return rc;
-    BatchGuard bg(L);
-    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
-                            const_cast<uint32_t*>(dKeys), nullptr, dSim, false, 0.0f, (hipStream_t)stream);
+    return ngsSimilarityDeviceM(handle, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, kSimLevenshtein,
+                                dSim, nullptr, stream);
 }
 
 NGS_API int ngsRerankDevice(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
                             uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
                             float* dSim, float minSimilarity, void* stream) {
-    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
-        stride > kRerankMaxStride || minSimilarity != minSimilarity)
-        return -3;
-    std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = nullptr;
-    Replica* R = nullptr;
-    if (const int rc = sim_entry(handle, L, R)) return rc;
-    BatchGuard bg(L);
-    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, true,
-                            minSimilarity, (hipStream_t)stream);
+    return ngsRerankDeviceM(handle, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim,
+                            nullptr, kSimLevenshtein, minSimilarity, stream);
 }
 
 NGS_API uint32_t scoreBatchSim(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
                                uint32_t limit, float minSimilarity, uint32_t* counts, char*** results, float** scores,
                                float** sims) {
-    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false);
+    return scoreBatchSimM(handle, queries, nQueries, threshold, limit, kSimLevenshtein, minSimilarity, counts, results,
+                          scores, sims, nullptr);
 }
 
 NGS_API uint32_t scoreBatchSimW(uint32_t handle, const wchar_t* const* queries, uint32_t nQueries, float threshold,
                                 uint32_t limit, float minSimilarity, uint32_t* counts, wchar_t*** results,
                                 float** scores, float** sims) {
-    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false);
+    return scoreBatchSimMW(handle, queries, nQueries, threshold, limit, kSimLevenshtein, minSimilarity, counts, results,
+                           scores, sims, nullptr);
 }
 
 NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
                                  uint32_t limit, float minSimilarity, uint32_t* counts, char*** results, float** scores,
                                  float** sims) {
-    return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, true);
+    return scoreBatchSimMU8(handle, queries, nQueries, threshold, limit, kSimLevenshtein, minSimilarity, counts,
+                            results, scores, sims, nullptr);
 }
 
 NGS_API int ngsSimilarityDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
@@ -3276,11 +3276,12 @@ NGS_API int ngsSimilarityDeviceM(uint32_t handle, const uint8_t* dQueryBytes, co
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = nullptr;
     Replica* R = nullptr;
-    if (const int rc = sim_entry(handle, L, R)) return rc;
+    if (const int rc = entry_library(handle, L)) return rc;
+    if (const int rc = entry_replica(*L, R)) return rc;
     BatchGuard bg(L);
     return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
-                            const_cast<uint32_t*>(dKeys), nullptr, dSim, false, 0.0f, (hipStream_t)stream, true, metric,
-                            dTerms);
+                            const_cast<uint32_t*>(dKeys), nullptr, dSim, dTerms, metric, false, 0.0f,
+                            (hipStream_t)stream);
 }
 
 NGS_API int ngsRerankDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
@@ -3292,40 +3293,40 @@ NGS_API int ngsRerankDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const 
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = nullptr;
     Replica* R = nullptr;
-    if (const int rc = sim_entry(handle, L, R)) return rc;
+    if (const int rc = entry_library(handle, L)) return rc;
+    if (const int rc = entry_replica(*L, R)) return rc;
     BatchGuard bg(L);
-    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, true,
-                            minSimilarity, (hipStream_t)stream, true, metric, dTerms);
+    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, dTerms,
+                            metric, true, minSimilarity, (hipStream_t)stream);
 }
 
 NGS_API uint32_t scoreBatchSimM(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
                                 uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts, char*** results,
                                 float** scores, float** sims, uint32_t** terms) {
     return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false,
-                     true, metric, terms);
+                     metric, terms);
 }
 
 NGS_API uint32_t scoreBatchSimMW(uint32_t handle, const wchar_t* const* queries, uint32_t nQueries, float threshold,
                                  uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
                                  wchar_t*** results, float** scores, float** sims, uint32_t** terms) {
     return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, false,
-                     true, metric, terms);
+                     metric, terms);
 }
 
 NGS_API uint32_t scoreBatchSimMU8(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
                                   uint32_t limit, uint32_t metric, float minSimilarity, uint32_t* counts,
                                   char*** results, float** scores, float** sims, uint32_t** terms) {
     return sim_batch(handle, queries, nQueries, threshold, limit, minSimilarity, counts, results, scores, sims, true,
-                     true, metric, terms);
+                     metric, terms);
 }
 
 NGS_API void ngsReleaseTerms(uint32_t* terms) { delete[] terms; }
 
 NGS_API int64_t ngsTerm(uint32_t handle, uint32_t termId, void* buf, uint64_t capBytes) {
     std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = find_lib(handle);
-    if (!L) return -1;
-    if (!L->host.indexed) return -2;
+    Library* L = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
     if (termId >= L->host.n_terms) return -3;
     BatchGuard bg(L);
     Replica& R = *L->reps.front();
@@ -3356,14 +3357,13 @@ NGS_API int ngsKeyQueriesDevice(uint32_t handle, uint32_t firstKey, uint32_t nKe
                                 uint64_t* dOffsets, void* stream) {
     if (!dOffsets || (capBytes && !dBytes)) return -3;
     std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = find_lib(handle);
-    if (!L) return -1;
-    if (!L->host.indexed) return -2;
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
     if (!join_range_ok(*L, firstKey, nKeys)) return -3;
     const uint64_t total = join_query_bytes(*L, firstKey, nKeys);
     if (capBytes < total || (L->host.csize == 4 && (reinterpret_cast<uintptr_t>(dBytes) & 3u))) return -3;
-    Replica* R = nullptr;
-    if (const int rc = sim_entry(handle, L, R)) return rc;
+    if (const int rc = entry_replica(*L, R)) return rc;
     BatchGuard bg(L);
     return HIP_CHECK(launch_key_queries(R->dev, firstKey, nKeys, total, dBytes, dOffsets, (hipStream_t)stream)) ? 0 : -4;
 }
@@ -3380,18 +3380,18 @@ NGS_API int ngsSelfJoinDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = nullptr;
     Replica* R = nullptr;
-    const int rc = sim_entry(handle, L, R);
-    if (rc == -1 || rc == -2) return rc;
+    if (const int rc = entry_library(handle, L)) return rc;
     if (!join_range_ok(*L, firstKey, nKeys) || outStride < join_search_limit(*L, limit)) return -3;
-    if (rc) return rc;
+    if (const int rc = entry_replica(*L, R)) return rc;
     if (nKeys == 0) return 0;
     BatchGuard bg(L);
-    // the call's own scratch: the gathered queries, released once the search has read them
-    SimBuffers M;
-    uint8_t* d_raw = nullptr;
-    uint64_t* d_off = nullptr;
-    if (!M.alloc(&d_raw, join_query_bytes(*L, firstKey, nKeys) + 16) || !M.alloc(&d_off, (size_t)nKeys + 1)) return -4;
-    return join_batch(*L, *R, firstKey, nKeys, threshold, limit, outStride, d_raw, d_off, dCounts, dKeys, dScores,
+    // the call's own scratch: the gathered queries, released once the search has read them (the
+    // results and the stream are the caller's)
+    CallScratch M;
+    if (!M.alloc(&M.d_raw, join_max_query_bytes(*L, firstKey, nKeys, nKeys) + 16) ||
+        !M.alloc(&M.d_off, (size_t)nKeys + 1))
+        return -4;
+    return join_batch(*L, *R, firstKey, nKeys, threshold, limit, outStride, M.d_raw, M.d_off, dCounts, dKeys, dScores,
                       (hipStream_t)stream, true);
 }
 
@@ -3411,12 +3411,12 @@ NGS_API uint32_t selfJoin(uint32_t handle, uint32_t firstKey, uint32_t nKeys, fl
 
 NGS_API uint32_t dedupKeys(uint32_t handle, float threshold, uint32_t limit, float minSimilarity, uint32_t batchKeys,
                            uint32_t* labels) {
-    return dedup_host(handle, threshold, limit, minSimilarity, batchKeys, labels);
+    return dedupKeysM(handle, threshold, limit, kSimLevenshtein, minSimilarity, batchKeys, labels);
 }
 
 NGS_API uint32_t dedupKeysM(uint32_t handle, float threshold, uint32_t limit, uint32_t metric, float minSimilarity,
                             uint32_t batchKeys, uint32_t* labels) {
-    return dedup_host(handle, threshold, limit, minSimilarity, batchKeys, labels, true, metric);
+    return dedup_host(handle, threshold, limit, metric, minSimilarity, batchKeys, labels);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

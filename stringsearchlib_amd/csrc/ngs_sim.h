@@ -11,13 +11,12 @@
 // key's terms. Wildcard queries score kSimWildcard on every record; a query of more than
 // kSimMaxQuery characters, or a key id outside the index, kSimNone ("not computed").
 //
-//
-// The M entry points select d and the divisor by a metric: kSimLevenshtein is the
-// above; kSimOsa adds the adjacent transposition at cost 1 (optimal string alignment: no substring
-// is edited twice), same divisor; kSimPartial is the semi-global form, d = the least Levenshtein
-// distance of Q to any substring of T (the empty one included, so d <= m), sim = 1 - d / m for
-// m >= 1 and 0 for m = 0. The matched term is the term id that attains a record's similarity, the
-// smallest such id; kSimNoTerm where no term was compared.
+// A metric selects d and the divisor: kSimLevenshtein is the above, and what the
+// entry points without a metric compute; kSimOsa adds the adjacent transposition at cost 1
+// (optimal string alignment: no substring is edited twice), same divisor; kSimPartial is the
+// semi-global form, d = the least Levenshtein distance of Q to any substring of T (the empty one
+// included, so d <= m), sim = 1 - d / m for m >= 1 and 0 for m = 0. The matched term is the term id
+// that attains a record's similarity, the smallest such id; kSimNoTerm where no term was compared.
 //
 // Plain C++17 without a HIP include: g++ compiles the host routines alone (tests/sanitize).
 #pragma once
@@ -277,22 +276,17 @@ NGS_HD inline uint64_t rerank_key(uint32_t sim_bits, uint32_t pos) {
 }
 
 #if defined(__HIPCC__)
-// dSim[i * stride + r], r < min(dCounts[i], stride): the similarity of query i and key dKeys[i * stride + r].
+// dSim[i * stride + r], r < min(dCounts[i], stride): the similarity by `metric` (< kSimMetrics) of query i
+// and key dKeys[i * stride + r]; with terms != null the matched term ids in sim's layout.
 // key_term: term of each key (indexes without kt_off), else null. Queues on s; no host wait.
 hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term,
                              const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
-                             const uint32_t* counts, const uint32_t* keys, float* sim, hipStream_t s);
-// ... by `metric` (< kSimMetrics), and with terms != null the matched term ids in sim's layout
-hipError_t launch_similarity_m(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term,
-                               const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
-                               const uint32_t* counts, const uint32_t* keys, uint32_t metric, float* sim,
-                               uint32_t* terms, hipStream_t s);
-// per query: records with sim < min_sim dropped, the rest ordered (sim desc, position asc), in place
+                             const uint32_t* counts, const uint32_t* keys, uint32_t metric, float* sim,
+                             uint32_t* terms, hipStream_t s);
+// per query: records with sim < min_sim dropped, the rest ordered (sim desc, position asc), in place,
+// the matched terms (may be null) permuted with them
 hipError_t launch_rerank(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
-                         float min_sim, hipStream_t s);
-// ... the matched terms (may be null) permuted with them
-hipError_t launch_rerank_m(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
-                           uint32_t* terms, float min_sim, hipStream_t s);
+                         uint32_t* terms, float min_sim, hipStream_t s);
 // key_term[k] = the term of key k's pair (kSimEmpty: none) of an index whose keys have one pair each
 hipError_t build_key_term(const DevIndex& X, uint32_t* key_term, hipStream_t s);
 #endif

@@ -11,8 +11,8 @@
 //             one step earlier.
 // k_rerank: one workgroup per query sorts (sim desc, position asc) in LDS and permutes in place.
 // The metric (ngs_sim.h: Levenshtein, OSA, partial) and the matched-term output are template
-// parameters of k_sim, the term array one of k_rerank: the entry points of §9.2
-// launch the instantiations <wide, kSimLevenshtein, false> and <false>, which are what they were.
+// parameters of k_sim, the term array one of k_rerank: launch_similarity and
+// launch_rerank pick the instantiation; the entry points without a metric are kSimLevenshtein, no terms.
 #include <hip/hip_runtime.h>
 
 #include "ngs_common.h"
@@ -500,18 +500,6 @@ __global__ __launch_bounds__(256) void k_key_term(DevIndex X, uint32_t* __restri
 
 }  // namespace
 
-hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term, const uint8_t* raw,
-                             const uint64_t* off, uint32_t n, uint32_t stride, const uint32_t* counts,
-                             const uint32_t* keys, float* sim, hipStream_t s) {
-    if (!n || !stride) return hipSuccess;
-    if (!X.kt_off && !key_term) return hipErrorInvalidValue;
-    SimArgs A{raw, off, counts, keys, sim, nullptr, key_term, n, stride, {}};
-    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
-    if (X.csize == 4) hipLaunchKernelGGL(k_sim<true>, dim3(n), dim3(64), 0, s, X, A);
-    else hipLaunchKernelGGL(k_sim<false>, dim3(n), dim3(64), 0, s, X, A);
-    return hipGetLastError();
-}
-
 namespace {
 template <uint32_t kMetric, bool kTerms>
 void launch_sim_as(const DevIndex& X, const SimArgs& A, hipStream_t s) {
@@ -525,9 +513,9 @@ void launch_sim_by_terms(const DevIndex& X, const SimArgs& A, hipStream_t s) {
 }
 }  // namespace
 
-hipError_t launch_similarity_m(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term, const uint8_t* raw,
-                               const uint64_t* off, uint32_t n, uint32_t stride, const uint32_t* counts,
-                               const uint32_t* keys, uint32_t metric, float* sim, uint32_t* terms, hipStream_t s) {
+hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const uint32_t* key_term, const uint8_t* raw,
+                             const uint64_t* off, uint32_t n, uint32_t stride, const uint32_t* counts,
+                             const uint32_t* keys, uint32_t metric, float* sim, uint32_t* terms, hipStream_t s) {
     if (metric >= kSimMetrics) return hipErrorInvalidValue;
     if (!n || !stride) return hipSuccess;
     if (!X.kt_off && !key_term) return hipErrorInvalidValue;
@@ -540,12 +528,7 @@ hipError_t launch_similarity_m(const DevIndex& X, const uint32_t valid[8], const
 }
 
 hipError_t launch_rerank(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
-                         float min_sim, hipStream_t s) {
-    return launch_rerank_m(n, stride, counts, keys, scores, sim, nullptr, min_sim, s);
-}
-
-hipError_t launch_rerank_m(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,
-                           uint32_t* terms, float min_sim, hipStream_t s) {
+                         uint32_t* terms, float min_sim, hipStream_t s) {
     if (!n) return hipSuccess;
     if (stride > kRerankMaxStride) return hipErrorInvalidValue;
     const uint32_t n2 = rerank_pow2(stride);  // every count's sort fits: counts are read as at most the stride

@@ -58,6 +58,27 @@ def _check(what: str) -> None:
         raise RuntimeError(f"{what} failed: HIP error {e} (see stderr)")
 
 
+def _ok(rc: int, what: str, exc=RuntimeError) -> None:
+    """Raise if a call that answers a return code answered a non-zero one."""
+    if rc:
+        raise exc(f"{what} failed: {rc}")
+
+
+def _cut(counts, nq: int, total: int, *columns):
+    """Flat result arrays -> one list per query: query i takes the next counts[i] places of every
+    column. A column is an indexable or (indexable, convert). One column gives lists of values, several
+    lists of tuples. The counts must add up to `total`."""
+    cols = [c if isinstance(c, tuple) else (c, None) for c in columns]
+    out, o = [], 0
+    for i in range(nq):
+        c = counts[i]
+        rows = [[f(a[j]) if f else a[j] for j in range(o, o + c)] for a, f in cols]
+        out.append(rows[0] if len(rows) == 1 else list(zip(*rows)))
+        o += c
+    assert o == total
+    return out
+
+
 class StringIndex:
     """One index of byte strings. gram_size 3 is the reference (indexN); 1 or 2 use the indexG
     extension (every reference threshold scaled by the gram size)."""
@@ -94,9 +115,7 @@ class StringIndex:
     def save(self, path) -> None:
         """Writes the index to `path` (ngsSaveIndex): the interned library; `load` rebuilds the
         rest on the GPU."""
-        rc = _native.lib().ngsSaveIndex(self.handle, os.fsencode(path))
-        if rc:
-            raise OSError(f"ngsSaveIndex({path!r}) failed: {rc}")
+        _ok(_native.lib().ngsSaveIndex(self.handle, os.fsencode(path)), f"ngsSaveIndex({path!r})", OSError)
 
     @classmethod
     def load(cls, path, devices=None):
@@ -104,9 +123,7 @@ class StringIndex:
         L = _native.lib()
         if devices is not None:
             ds = (C.c_int * max(1, len(devices)))(*devices)
-            rc = L.ngsSetDevices(ds, len(devices))
-            if rc:
-                raise RuntimeError(f"ngsSetDevices({list(devices)}) failed: {rc}")
+            _ok(L.ngsSetDevices(ds, len(devices)), f"ngsSetDevices({list(devices)})")
         try:
             handle = L.ngsLoadIndex(os.fsencode(path))
         finally:
@@ -220,35 +237,10 @@ class StringIndex:
         metric: "levenshtein" (the default), "osa" or "partial", or NGS_SIM_*'s integer (scoreBatchSimM).
         with_terms: every result is (key, score, sim, term), term the matched term's string as `term`
         returns it, None where no term was compared."""
-        if metric is not None or with_terms:
-            return self._score_batch_sim_m(queries, threshold, limit, min_similarity,
-                                           _metric("levenshtein" if metric is None else metric), with_terms)
-        L, f = _native.lib(), self._fn
-        nq = len(queries)
-        qs = self._queries(queries)
-        counts = (C.c_uint32 * max(1, nq))()
-        res = self._RES()
-        sc = C.POINTER(C.c_float)()
-        sv = C.POINTER(C.c_float)()
-        L.ngsLastError(1)
-        total = getattr(L, f["scoreBatchSim"])(self.handle, qs, nq, threshold, limit, min_similarity, counts,
-                                               C.byref(res), C.byref(sc), C.byref(sv))
-        if not total:
-            _check(f["scoreBatchSim"])
-        out, o = [], 0
-        for i in range(nq):
-            c = counts[i]
-            out.append([(self._string(res[o + j]), sc[o + j], sv[o + j]) for j in range(c)])
-            o += c
-        assert o == total
-        if res:
-            getattr(L, f["release"])(self.handle, res, sc)
-        if sv:
-            getattr(L, f["release"])(self.handle, None, sv)
-        return out
-
-    def _score_batch_sim_m(self, queries, threshold, limit, min_similarity, metric: int, with_terms: bool):
-        L, f = _native.lib(), self._fn
+        by_metric = metric is not None or with_terms
+        m = _metric("levenshtein" if metric is None else metric)
+        L = _native.lib()
+        fn = self._fn["scoreBatchSimM" if by_metric else "scoreBatchSim"]
         nq = len(queries)
         qs = self._queries(queries)
         counts = (C.c_uint32 * max(1, nq))()
@@ -256,12 +248,15 @@ class StringIndex:
         sc = C.POINTER(C.c_float)()
         sv = C.POINTER(C.c_float)()
         tv = C.POINTER(C.c_uint32)()
+        out_args = (counts, C.byref(res), C.byref(sc), C.byref(sv))
         L.ngsLastError(1)
-        total = getattr(L, f["scoreBatchSimM"])(self.handle, qs, nq, threshold, limit, metric, min_similarity, counts,
-                                                C.byref(res), C.byref(sc), C.byref(sv),
-                                                C.byref(tv) if with_terms else None)
+        if by_metric:
+            total = getattr(L, fn)(self.handle, qs, nq, threshold, limit, m, min_similarity, *out_args,
+                                   C.byref(tv) if with_terms else None)
+        else:
+            total = getattr(L, fn)(self.handle, qs, nq, threshold, limit, min_similarity, *out_args)
         if not total:
-            _check(f["scoreBatchSimM"])
+            _check(fn)
         names: dict = {}  # term id -> string: one ngsTerm call per distinct term
 
         def name(t):
@@ -271,19 +266,12 @@ class StringIndex:
                 names[t] = self.term(t)
             return names[t]
 
-        out, o = [], 0
-        for i in range(nq):
-            c = counts[i]
-            if with_terms:
-                out.append([(self._string(res[o + j]), sc[o + j], sv[o + j], name(tv[o + j])) for j in range(c)])
-            else:
-                out.append([(self._string(res[o + j]), sc[o + j], sv[o + j]) for j in range(c)])
-            o += c
-        assert o == total
+        out = _cut(counts, nq, total, (res, self._string), sc, sv, *([(tv, name)] if with_terms else []))
+        release = getattr(L, self._fn["release"])
         if res:
-            getattr(L, f["release"])(self.handle, res, sc)
+            release(self.handle, res, sc)
         if sv:
-            getattr(L, f["release"])(self.handle, None, sv)
+            release(self.handle, None, sv)
         if tv:
             L.ngsReleaseTerms(tv)
         return out
@@ -353,28 +341,20 @@ class StringIndex:
     def search_device(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int, out_stride: int,
                       d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> None:
         """ngsSearchDevice on raw device pointers (e.g. torch tensors' data_ptr())."""
-        rc = _native.lib().ngsSearchDevice(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
-                                           d_counts, d_keys, d_scores, stream or None)
-        if rc:
-            raise RuntimeError(f"ngsSearchDevice failed: {rc}")
-
+        _ok(_native.lib().ngsSearchDevice(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
+                                          d_counts, d_keys, d_scores, stream or None), "ngsSearchDevice")
 
     def similarity_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
                           d_sim: int, stream: int = 0, metric=None, d_terms: int = 0) -> None:
         """ngsSimilarityDevice on raw device pointers: d_sim[i * stride + r] = the edit-distance similarity of
         query i and key d_keys[i * stride + r], r < d_counts[i]; queued on `stream`, nothing waits.
         With a metric or d_terms (the matched term ids, in d_sim's layout): ngsSimilarityDeviceM."""
+        L, head = _native.lib(), (self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys)
         if metric is not None or d_terms:
-            rc = _native.lib().ngsSimilarityDeviceM(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys,
-                                                    _metric("levenshtein" if metric is None else metric), d_sim,
-                                                    d_terms or None, stream or None)
-            if rc:
-                raise RuntimeError(f"ngsSimilarityDeviceM failed: {rc}")
-            return
-        rc = _native.lib().ngsSimilarityDevice(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_sim,
-                                               stream or None)
-        if rc:
-            raise RuntimeError(f"ngsSimilarityDevice failed: {rc}")
+            _ok(L.ngsSimilarityDeviceM(*head, _metric("levenshtein" if metric is None else metric), d_sim,
+                                       d_terms or None, stream or None), "ngsSimilarityDeviceM")
+        else:
+            _ok(L.ngsSimilarityDevice(*head, d_sim, stream or None), "ngsSimilarityDevice")
 
     def rerank_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
                       d_scores: int, d_sim: int, min_similarity: float = 0.0, stream: int = 0, metric=None,
@@ -382,18 +362,12 @@ class StringIndex:
         """ngsRerankDevice on raw device pointers: the similarity, then every query's records filtered by
         min_similarity and ordered by (sim descending, position ascending), in place; queued on `stream`.
         With a metric or d_terms (the matched term ids, permuted with the records): ngsRerankDeviceM."""
+        L, head = _native.lib(), (self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores, d_sim)
         if metric is not None or d_terms:
-            rc = _native.lib().ngsRerankDeviceM(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores,
-                                                d_sim, d_terms or None,
-                                                _metric("levenshtein" if metric is None else metric), min_similarity,
-                                                stream or None)
-            if rc:
-                raise RuntimeError(f"ngsRerankDeviceM failed: {rc}")
-            return
-        rc = _native.lib().ngsRerankDevice(self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores,
-                                           d_sim, min_similarity, stream or None)
-        if rc:
-            raise RuntimeError(f"ngsRerankDevice failed: {rc}")
+            _ok(L.ngsRerankDeviceM(*head, d_terms or None, _metric("levenshtein" if metric is None else metric),
+                                   min_similarity, stream or None), "ngsRerankDeviceM")
+        else:
+            _ok(L.ngsRerankDevice(*head, min_similarity, stream or None), "ngsRerankDevice")
 
     # -- self-join: near-duplicate keys and their clusters (include/ngram_search.h) ----------
     def self_join(self, first: int = 0, count: int | None = None, threshold: float = 0.0, limit: int = 10):
@@ -444,28 +418,22 @@ class StringIndex:
                            stream: int = 0) -> None:
         """ngsKeyQueriesDevice on raw device pointers: those keys in search_device's query layout, queued
         on `stream`."""
-        rc = _native.lib().ngsKeyQueriesDevice(self.handle, first, count, d_bytes or None, cap_bytes, d_offsets,
-                                               stream or None)
-        if rc:
-            raise RuntimeError(f"ngsKeyQueriesDevice failed: {rc}")
+        _ok(_native.lib().ngsKeyQueriesDevice(self.handle, first, count, d_bytes or None, cap_bytes, d_offsets,
+                                              stream or None), "ngsKeyQueriesDevice")
 
     @staticmethod
     def drop_self_device(d_counts: int, d_keys: int, d_scores: int, n: int, stride: int, first: int, limit: int = 0,
                          stream: int = 0) -> None:
         """ngsDropSelfDevice on raw device pointers: row i loses the record of key first + i and is cut to
         `limit` (0: no cut), in place; queued on `stream`."""
-        rc = _native.lib().ngsDropSelfDevice(d_counts, d_keys or None, d_scores or None, n, stride, first, limit,
-                                             stream or None)
-        if rc:
-            raise RuntimeError(f"ngsDropSelfDevice failed: {rc}")
+        _ok(_native.lib().ngsDropSelfDevice(d_counts, d_keys or None, d_scores or None, n, stride, first, limit,
+                                            stream or None), "ngsDropSelfDevice")
 
     def self_join_device(self, first: int, count: int, threshold: float, limit: int, out_stride: int, d_counts: int,
                          d_keys: int, d_scores: int, stream: int = 0) -> None:
         """ngsSelfJoinDevice on raw device pointers; out_stride >= min((limit or 2^31-1) + 1, keys)."""
-        rc = _native.lib().ngsSelfJoinDevice(self.handle, first, count, threshold, limit, out_stride, d_counts,
-                                             d_keys or None, d_scores or None, stream or None)
-        if rc:
-            raise RuntimeError(f"ngsSelfJoinDevice failed: {rc}")
+        _ok(_native.lib().ngsSelfJoinDevice(self.handle, first, count, threshold, limit, out_stride, d_counts,
+                                            d_keys or None, d_scores or None, stream or None), "ngsSelfJoinDevice")
 
     @staticmethod
     def cluster_device(d_counts: int, d_keys: int, n: int, stride: int, first: int, d_labels: int, n_labels: int,
@@ -473,26 +441,22 @@ class StringIndex:
         """ngsClusterDevice on raw device pointers: the block's (first + i, key) records merged into the
         label forest d_labels[n_labels]; `init` sets labels[k] = k first, `finish` makes every label the
         smallest id of its component. Queued on `stream`."""
-        rc = _native.lib().ngsClusterDevice(d_counts or None, d_keys or None, n, stride, first, d_labels or None,
-                                            n_labels, (1 if init else 0) | (2 if finish else 0), stream or None)
-        if rc:
-            raise RuntimeError(f"ngsClusterDevice failed: {rc}")
+        _ok(_native.lib().ngsClusterDevice(d_counts or None, d_keys or None, n, stride, first, d_labels or None,
+                                           n_labels, (1 if init else 0) | (2 if finish else 0), stream or None),
+            "ngsClusterDevice")
 
     def search_device_async(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int,
                             out_stride: int, d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> int:
         """ngsSearchDeviceAsync: queues the search and returns its ticket (wait_device(ticket))."""
         t = C.c_uint64()
-        rc = _native.lib().ngsSearchDeviceAsync(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
-                                                d_counts, d_keys, d_scores, stream or None, C.byref(t))
-        if rc:
-            raise RuntimeError(f"ngsSearchDeviceAsync failed: {rc}")
+        _ok(_native.lib().ngsSearchDeviceAsync(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
+                                               d_counts, d_keys, d_scores, stream or None, C.byref(t)),
+            "ngsSearchDeviceAsync")
         return t.value
 
     def wait_device(self, ticket: int) -> None:
         """ngsSearchDeviceWait: the results of that call are complete on return."""
-        rc = _native.lib().ngsSearchDeviceWait(self.handle, ticket)
-        if rc:
-            raise RuntimeError(f"ngsSearchDeviceWait failed: {rc}")
+        _ok(_native.lib().ngsSearchDeviceWait(self.handle, ticket), "ngsSearchDeviceWait")
 
 
 # ---- wide strings (indexW extension) ---------------------------------------------------
@@ -580,9 +544,8 @@ def utf8_decode_device(d_bytes: int, d_offsets: int, n: int, d_out: int, out_cap
                        stream: int = 0) -> None:
     """ngsUtf8Decode on raw device pointers: n UTF-8 strings (absolute byte offsets) -> UTF-32
     characters in d_out and their byte offsets (from 0) in d_out_offsets, queued on `stream`."""
-    rc = _native.lib().ngsUtf8Decode(d_bytes, d_offsets, n, d_out, out_cap_bytes, d_out_offsets, stream or None)
-    if rc:
-        raise RuntimeError(f"ngsUtf8Decode failed: {rc}")
+    _ok(_native.lib().ngsUtf8Decode(d_bytes, d_offsets, n, d_out, out_cap_bytes, d_out_offsets, stream or None),
+        "ngsUtf8Decode")
 
 
 class Utf8StringIndex(WideStringIndex):
@@ -615,7 +578,5 @@ class Utf8StringIndex(WideStringIndex):
     def search_device_u8(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int, out_stride: int,
                          d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> None:
         """ngsSearchDeviceU8: search_device with UTF-8 query bytes and offsets."""
-        rc = _native.lib().ngsSearchDeviceU8(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
-                                             d_counts, d_keys, d_scores, stream or None)
-        if rc:
-            raise RuntimeError(f"ngsSearchDeviceU8 failed: {rc}")
+        _ok(_native.lib().ngsSearchDeviceU8(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
+                                            d_counts, d_keys, d_scores, stream or None), "ngsSearchDeviceU8")
