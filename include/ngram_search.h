@@ -471,6 +471,46 @@ NGS_API uint32_t dedupKeysM(uint32_t handle, float threshold, uint32_t limit, ui
  * -4 HIP error. */
 NGS_API int64_t ngsTerm(uint32_t handle, uint32_t termId, void* buf, uint64_t capBytes);
 
+/* ------------------------------------------------------------------------------------
+ * Token sort: a similarity that does not depend on the order of the words (not in the reference).
+ * NGS_SIM_TOKEN_SORT is OR'ed onto one of the three metrics above (a metric is valid iff
+ * (metric & ~NGS_SIM_TOKEN_SORT) <= 2; anything else is unknown as before). A record's similarity
+ * is then the base metric's sim(Q', T') with the divisor from m' = |Q'| and L' = |T'|, the largest
+ * over the key's non-empty terms; the matched term is the ordinary term id; wildcard rows, -1.0f
+ * rows and everything else are as above. ngsTerm still returns the term as indexed.
+ *
+ * The token-sorted form of a string: split it at its separators into tokens (the maximal runs of
+ * the other characters), order the tokens by their normalised characters (unsigned values,
+ * lexicographically, a proper prefix first, equal tokens in their order of appearance), join them
+ * with single blanks. For a query a separator is a character that is blank after the validChar
+ * escape, and the characters written are the raw ones; for a term T as the index stores it a
+ * separator is a blank, and L' <= L. A string of more than 4,096 characters between its first and
+ * last token character stays as it is (the similarity answers -1.0f for such a query), and so does
+ * the query "*", which is a wildcard whether or not the validChar set keeps '*'.
+ *
+ * scoreBatchSimM / MW / MU8 and dedupKeysM sort their queries themselves. The two device entry
+ * points, ngsSimilarityDeviceM and ngsRerankDeviceM, do NOT: with the flag they read the
+ * token-sorted terms and take the query bytes as given, because they must not wait for the host
+ * and the host does not know the batch's byte count. Queue ngsTokenSortDevice on the same stream in
+ * front of them (as ngsUtf8Decode goes in front of ngsSearchDevice), behind the search, which needs
+ * the queries as they were. The first flagged call on a device builds the sorted terms of the
+ * index's copy there, once, synchronously (about the size of the terms themselves).
+ * ------------------------------------------------------------------------------------ */
+#define NGS_SIM_TOKEN_SORT 0x100u
+
+/* Token-sorts a query batch in ngsSearchDevice's layout: string i, dBytes[dOffsets[i] .. dOffsets[i+1])
+ * (bytes on a narrow handle, UTF-32 units at offsets in multiples of 4 on a wide one), is written to
+ * dOut at the same offsets: the tokens' raw characters in sorted order, one ' ' (0x20) between
+ * neighbours, then ' ' up to the string's length. The length is kept, so "" and "*" stay the
+ * wildcards they were, "   " stays three blanks and " *" becomes "* " (or two blanks where the validChar
+ * set does not keep '*'), which is no wildcard. The
+ * handle supplies the character width and the validChar set as of the call. dOut may be dBytes (in
+ * place); nothing outside [dOffsets[0], dOffsets[n]) is written. Queued on `stream`; nothing waits.
+ * 0 ok (n = 0 included), -3 NULL dOffsets, or NULL dBytes or dOut with n > 0, -1 bad handle,
+ * -2 un-built index, -4 HIP error. */
+NGS_API int ngsTokenSortDevice(uint32_t handle, const uint8_t* dBytes, const uint64_t* dOffsets, uint32_t n,
+                               uint8_t* dOut, void* stream);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);

@@ -143,6 +143,8 @@ EXPORTS = [
                               "ngsReleaseTerms": (None, [PU]),
                               "dedupKeysM": (u32, [u32, f32, u32, u32, f32, u32, PU]),
                               "ngsTerm": (C.c_int64, [u32, u32, vp, u64])}),
+    # the token sort in front of the similarity
+    ("ngsTokenSortDevice", {"ngsTokenSortDevice": (ci, [u32, vp, vp, u32, vp, vp])}),
     # the self-join
     ("ngsSelfJoinDevice", {"ngsKeyQueryBytes": (u64, [u32, u32, u32]),
                            "ngsKeyQueriesDevice": (ci, [u32, u32, u32, vp, u64, vp, vp]),

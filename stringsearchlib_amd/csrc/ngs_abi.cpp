@@ -30,6 +30,7 @@
 #include "ngs_join.h"
 #include "ngs_kernels.h"
 #include "ngs_sim.h"
+#include "ngs_token.h"
 #include "ngs_utf8.h"
 
 namespace ngs {
@@ -435,6 +436,10 @@ struct Replica {
     // built from tk on the device by the first similarity call on the replica (sim_key_term)
     std::mutex sim_mu;
     const uint32_t* key_term = nullptr;
+    // the token-sorted terms (NGS_SIM_TOKEN_SORT): term_off / term_bytes of the terms' sorted forms,
+    // built from the device's term arrays by the first flagged call on the replica (sim_sorted_terms)
+    const uint64_t* ts_off = nullptr;
+    const uint8_t* ts_bytes = nullptr;
 
     // the index as the kernels of a search under `valid` see it (kt_flag for that set); false on a
     // HIP failure
@@ -2450,6 +2455,41 @@ const uint32_t* sim_key_term(Replica& R, bool& ok) {
     return kt;
 }
 
+// The token-sorted terms of replica R for a flagged similarity call: ts_off[n_terms
+// + 1] and ts_bytes, in term_off / term_bytes' layout (character offsets; two dwords of padding
+// behind the last term, which myers_narrow reads ahead into). The first flagged call builds them
+// from the device's own term arrays: pass 1 the lengths and their scan, pass 2 the characters;
+// synchronously on the null stream, published once and kept until dispose, as key_term is.
+// R's device is current. False on a HIP failure.
+bool sim_sorted_terms(Replica& R, DevIndex& X) {
+    std::lock_guard<std::mutex> g(R.sim_mu);
+    if (!R.ts_off) {
+        const uint64_t cs = R.dev.csize;
+        uint64_t* off = nullptr;
+        uint8_t* bytes = nullptr;
+        uint64_t chars = 0;
+        auto own = [&](void* p) {
+            std::lock_guard<std::mutex> o(R.kflag_mu);  // (Replica::owned is shared with index_for)
+            R.owned.push_back(p);
+        };
+        if (!dev_alloc(&off, (size_t)R.dev.n_terms + 1)) return false;
+        own(off);
+        if (!HIP_CHECK(sorted_term_offsets(R.dev, off, nullptr)) ||
+            !HIP_CHECK(hipMemcpy(&chars, off + R.dev.n_terms, sizeof chars, hipMemcpyDeviceToHost)) ||
+            !dev_alloc(&bytes, (size_t)(chars * cs) + 8))
+            return false;
+        own(bytes);
+        if (!HIP_CHECK(hipMemsetAsync(bytes + chars * cs, 0, 8, nullptr)) ||
+            !HIP_CHECK(launch_sorted_terms(R.dev, off, bytes, nullptr)) || !HIP_CHECK(hipStreamSynchronize(nullptr)))
+            return false;
+        R.ts_bytes = bytes;
+        R.ts_off = off;
+    }
+    X.term_off = R.ts_off;
+    X.term_bytes = R.ts_bytes;
+    return true;
+}
+
 // the argument checks of the two device entry points, before any handle or device is touched
 bool sim_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint32_t* d_n, const uint32_t* d_k,
                  const float* d_v) {
@@ -2457,10 +2497,13 @@ bool sim_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint3
 }
 
 // Queues the similarity kernel by `metric` (and, with `rerank`, the re-rank behind it) on s; nothing
-// waits. d_t: the matched terms, or null.
+// waits. d_t: the matched terms, or null. With kSimTokenSort in `metric` the kernel reads the
+// replica's token-sorted terms, and with d_sort (= d_raw, writable: the host calls' own scratch) the
+// queries are token-sorted in place in front of it, under the same snapshot of the validChar set;
+// without d_sort they are taken as given (the device entry points).
 int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
                      uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, uint32_t* d_t, uint32_t metric, bool rerank,
-                     float min_sim, hipStream_t s) {
+                     float min_sim, hipStream_t s, uint8_t* d_sort = nullptr) {
     if (n == 0) return 0;
     bool ok = true;
     const uint32_t* key_term = sim_key_term(R, ok);
@@ -2470,8 +2513,17 @@ int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_
         std::lock_guard<std::mutex> g(L.valid_mu);
         std::memcpy(valid, L.valid, sizeof valid);
     }
-    if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, metric, d_v, d_t, s)))
+    if (metric & kSimTokenSort) {
+        DevIndex X = R.dev;
+        if (!sim_sorted_terms(R, X)) return -4;
+        if (d_sort && !HIP_CHECK(launch_token_sort(valid, X.csize, d_raw, d_off, n, d_sort, s))) return -4;
+        if (!HIP_CHECK(launch_similarity(X, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, sim_metric_base(metric),
+                                         d_v, d_t, s)))
+            return -4;
+    } else if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, metric, d_v, d_t,
+                                            s))) {
         return -4;
+    }
     if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
     return 0;
 }
@@ -2543,7 +2595,7 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
     Library* L = find_lib(handle);
     const uint32_t cs = u8 ? (uint32_t)sizeof(uint32_t) : (uint32_t)sizeof(CharT);
     if (!L || !L->host.indexed || !queries || !counts || !results || !scores || !sims || L->host.csize != cs) return 0;
-    if (min_sim != min_sim || metric >= kSimMetrics) {
+    if (min_sim != min_sim || !sim_metric_ok(metric)) {
         t_last_error = (int)hipErrorInvalidValue;
         return 0;
     }
@@ -2613,7 +2665,7 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
             return 0;
         }
         if (queue_similarity(*L, R, M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, metric, true, min_sim,
-                             M.stream) != 0)
+                             M.stream, M.d_raw) != 0)
             return 0;
         // 4. everything back
         const size_t rb = (size_t)B * Lm;
@@ -2753,7 +2805,7 @@ uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr,
 
 uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric, float min_sim, uint32_t batch_keys,
                     uint32_t* labels) {
-    if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim || metric >= kSimMetrics) {
+    if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim || !sim_metric_ok(metric)) {
         t_last_error = labels && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
         return 0;
     }
@@ -2785,7 +2837,7 @@ uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric,
             return 0;
         }
         if (verify && (queue_similarity(*L, R, M.d_raw, M.d_off, n, Ls, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric,
-                                        false, 0.0f, M.stream) != 0 ||
+                                        false, 0.0f, M.stream, M.d_raw) != 0 ||
                        !HIP_CHECK(launch_keep_similar(M.d_n, M.d_k, M.d_s, d_v, n, Ls, min_sim, M.stream))))
             return 0;
         const uint32_t flags = (done == 0 ? kClusterInit : 0u) | (done + n == nk ? kClusterFinish : 0u);
@@ -2983,6 +3035,21 @@ NGS_API int ngsUtf8Decode(const uint8_t* dBytes, const uint64_t* dOffsets, uint3
                                         dOutOffsets, t.first, t.second, (hipStream_t)stream))
                ? 0
                : -4;
+}
+
+NGS_API int ngsTokenSortDevice(uint32_t handle, const uint8_t* dBytes, const uint64_t* dOffsets, uint32_t n,
+                               uint8_t* dOut, void* stream) {
+    if (!dOffsets || (n && (!dBytes || !dOut))) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
+    BatchGuard bg(L);
+    uint32_t valid[8];
+    {
+        std::lock_guard<std::mutex> g(L->valid_mu);
+        std::memcpy(valid, L->valid, sizeof valid);
+    }
+    return HIP_CHECK(launch_token_sort(valid, L->host.csize, dBytes, dOffsets, n, dOut, (hipStream_t)stream)) ? 0 : -4;
 }
 
 NGS_API int ngsSearchDeviceU8(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
@@ -3272,7 +3339,7 @@ NGS_API uint32_t scoreBatchSimU8(uint32_t handle, const char* const* queries, ui
 NGS_API int ngsSimilarityDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
                                  uint32_t nQueries, uint32_t stride, const uint32_t* dCounts, const uint32_t* dKeys,
                                  uint32_t metric, float* dSim, uint32_t* dTerms, void* stream) {
-    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || metric >= kSimMetrics) return -3;
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || !sim_metric_ok(metric)) return -3;
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = nullptr;
     Replica* R = nullptr;
@@ -3288,7 +3355,7 @@ NGS_API int ngsRerankDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const 
                              uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
                              float* dSim, uint32_t* dTerms, uint32_t metric, float minSimilarity, void* stream) {
     if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
-        stride > kRerankMaxStride || minSimilarity != minSimilarity || metric >= kSimMetrics)
+        stride > kRerankMaxStride || minSimilarity != minSimilarity || !sim_metric_ok(metric))
         return -3;
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = nullptr;

@@ -28,19 +28,23 @@ NGS_ERR_RERANK_LIMIT = 0x10003
 
 # the similarity's metrics (NGS_SIM_* of include/ngram_search.h) and "no term was compared"
 METRICS = {"levenshtein": 0, "osa": 1, "partial": 2}
+TOKEN_SORT = 0x100  # NGS_SIM_TOKEN_SORT: OR'ed onto a metric
 NO_TERM = 0xFFFFFFFF
 
 
-def _metric(metric) -> int:
-    """"levenshtein" | "osa" | "partial" or the integer -> NGS_SIM_*."""
+def _metric(metric, token_sort: bool = False) -> int:
+    """"levenshtein" | "osa" | "partial" or the integer (with or without TOKEN_SORT) -> NGS_SIM_*,
+    with TOKEN_SORT set if token_sort."""
+    flag = TOKEN_SORT if token_sort else 0
     if isinstance(metric, str):
         if metric not in METRICS:
             raise ValueError(f"unknown metric {metric!r}: one of {sorted(METRICS)}")
-        return METRICS[metric]
+        return METRICS[metric] | flag
     m = int(metric)
-    if m not in METRICS.values():
-        raise ValueError(f"unknown metric {metric!r}: one of {sorted(METRICS.values())}")
-    return m
+    if (m & ~TOKEN_SORT) not in METRICS.values():
+        raise ValueError(f"unknown metric {metric!r}: one of {sorted(METRICS.values())}, with or without "
+                         f"TOKEN_SORT ({TOKEN_SORT:#x})")
+    return m | flag
 
 
 def _check(what: str) -> None:
@@ -230,15 +234,17 @@ class StringIndex:
         return out
 
     def score_batch_sim(self, queries, threshold: float = 0.0, limit: int = 100, min_similarity: float = 0.0,
-                        metric=None, with_terms: bool = False):
+                        metric=None, with_terms: bool = False, token_sort: bool = False):
         """scoreBatchSim: score_batch re-ranked by the edit-distance similarity (include/ngram_search.h):
         one list of (key, score, sim) per query, records with sim < min_similarity dropped, the rest in
         order of (sim descending, the search's order ascending). min(limit, keys) must be at most 4,096.
         metric: "levenshtein" (the default), "osa" or "partial", or NGS_SIM_*'s integer (scoreBatchSimM).
         with_terms: every result is (key, score, sim, term), term the matched term's string as `term`
-        returns it, None where no term was compared."""
-        by_metric = metric is not None or with_terms
-        m = _metric("levenshtein" if metric is None else metric)
+        returns it, None where no term was compared.
+        token_sort: the similarity of the token-sorted query and terms (NGS_SIM_TOKEN_SORT): the order of
+        the words does not count."""
+        by_metric = metric is not None or with_terms or token_sort
+        m = _metric("levenshtein" if metric is None else metric, token_sort)
         L = _native.lib()
         fn = self._fn["scoreBatchSimM" if by_metric else "scoreBatchSim"]
         nq = len(queries)
@@ -345,26 +351,37 @@ class StringIndex:
                                           d_counts, d_keys, d_scores, stream or None), "ngsSearchDevice")
 
     def similarity_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
-                          d_sim: int, stream: int = 0, metric=None, d_terms: int = 0) -> None:
+                          d_sim: int, stream: int = 0, metric=None, d_terms: int = 0, token_sort: bool = False) -> None:
         """ngsSimilarityDevice on raw device pointers: d_sim[i * stride + r] = the edit-distance similarity of
         query i and key d_keys[i * stride + r], r < d_counts[i]; queued on `stream`, nothing waits.
-        With a metric or d_terms (the matched term ids, in d_sim's layout): ngsSimilarityDeviceM."""
+        With a metric or d_terms (the matched term ids, in d_sim's layout): ngsSimilarityDeviceM.
+        token_sort sets NGS_SIM_TOKEN_SORT only: the token-sorted terms are read and the query bytes taken
+        as given (token_sort_device on the same stream first)."""
         L, head = _native.lib(), (self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys)
-        if metric is not None or d_terms:
-            _ok(L.ngsSimilarityDeviceM(*head, _metric("levenshtein" if metric is None else metric), d_sim,
+        if metric is not None or d_terms or token_sort:
+            _ok(L.ngsSimilarityDeviceM(*head, _metric("levenshtein" if metric is None else metric, token_sort), d_sim,
                                        d_terms or None, stream or None), "ngsSimilarityDeviceM")
         else:
             _ok(L.ngsSimilarityDevice(*head, d_sim, stream or None), "ngsSimilarityDevice")
 
+    def token_sort_device(self, d_bytes: int, d_offsets: int, n: int, d_out: int, stream: int = 0) -> None:
+        """ngsTokenSortDevice on raw device pointers: the n strings of a query batch token-sorted into d_out
+        at the same offsets (d_out may be d_bytes), under this index's width and validChar set; queued
+        on `stream`."""
+        _ok(_native.lib().ngsTokenSortDevice(self.handle, d_bytes or None, d_offsets or None, n, d_out or None,
+                                             stream or None), "ngsTokenSortDevice")
+
     def rerank_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
                       d_scores: int, d_sim: int, min_similarity: float = 0.0, stream: int = 0, metric=None,
-                      d_terms: int = 0) -> None:
+                      d_terms: int = 0, token_sort: bool = False) -> None:
         """ngsRerankDevice on raw device pointers: the similarity, then every query's records filtered by
         min_similarity and ordered by (sim descending, position ascending), in place; queued on `stream`.
-        With a metric or d_terms (the matched term ids, permuted with the records): ngsRerankDeviceM."""
+        With a metric or d_terms (the matched term ids, permuted with the records): ngsRerankDeviceM.
+        token_sort: as similarity_device's."""
         L, head = _native.lib(), (self.handle, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores, d_sim)
-        if metric is not None or d_terms:
-            _ok(L.ngsRerankDeviceM(*head, d_terms or None, _metric("levenshtein" if metric is None else metric),
+        if metric is not None or d_terms or token_sort:
+            _ok(L.ngsRerankDeviceM(*head, d_terms or None,
+                                   _metric("levenshtein" if metric is None else metric, token_sort),
                                    min_similarity, stream or None), "ngsRerankDeviceM")
         else:
             _ok(L.ngsRerankDevice(*head, min_similarity, stream or None), "ngsRerankDevice")
@@ -390,11 +407,15 @@ class StringIndex:
         return out
 
     def dedup(self, threshold: float, limit: int = 10, min_similarity: float | None = None, batch_keys: int = 0,
-              metric=None):
+              metric=None, token_sort: bool = False):
         """dedupKeys: labels[k] = the smallest key id of key k's cluster, the clusters being the
         connected components of the self-join at (threshold, limit); with min_similarity, of its records
         whose edit-distance similarity is at least that. limit in 1..4,096. metric: the similarity's
-        (dedupKeysM); "partial" is directional, and an edge is made if either key's row keeps it."""
+        (dedupKeysM); "partial" is directional, and an edge is made if either key's row keeps it.
+        token_sort: the similarity of the token-sorted strings, so keys whose words are in another order
+        join."""
+        if token_sort and metric is None:
+            metric = "levenshtein"
         L = _native.lib()
         nk = self.num_keys()
         labels = (C.c_uint32 * max(1, nk))()
@@ -403,7 +424,8 @@ class StringIndex:
         if metric is None:
             clusters = L.dedupKeys(self.handle, threshold, limit, ms, batch_keys, labels)
         else:
-            clusters = L.dedupKeysM(self.handle, threshold, limit, _metric(metric), ms, batch_keys, labels)
+            clusters = L.dedupKeysM(self.handle, threshold, limit, _metric(metric, token_sort), ms, batch_keys,
+                                    labels)
         if not clusters:
             _check("dedupKeys" if metric is None else "dedupKeysM")
         out = list(labels[:nk])

@@ -11,9 +11,15 @@ same stream. Records and term characters are counted on the host from the search
 --metric NAME (repeatable; "levenshtein", "osa" or "partial") times the same stage through
 ngsRerankDeviceM / ngsSimilarityDeviceM by that metric as well, alternating with the stage above
 within every repetition; --terms has those calls write the matched term ids too.
+--token-sort times, besides all that, ngsTokenSortDevice alone (out of place, HIP events) and the
+stage with NGS_SIM_TOKEN_SORT (the token sort of the batch and the flagged re-rank behind it) for
+Levenshtein and every --metric, alternating with the unflagged stages; the first flagged call, which
+builds the replica's token-sorted terms, is timed on the host clock and the arrays' bytes are
+computed from the library.
 Prints one JSON line.
 
     python tools/sim_probe.py [--rows 200000] [--queries 4096] [--reps 30] [--metric osa --metric partial] [--terms]
+                              [--token-sort]
 """
 import argparse
 import json
@@ -30,6 +36,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402  (one HIP runtime per process: torch's first)
 
 import sim_ref  # noqa: E402
+import token_ref  # noqa: E402
 import stringsearchlib_amd as ssl  # noqa: E402
 from stringsearchlib_amd import _native  # noqa: E402
 
@@ -56,6 +63,7 @@ def main():
     ap.add_argument("--min-similarity", type=float, default=0.0)
     ap.add_argument("--metric", action="append", default=[], choices=sorted(ssl.METRICS))
     ap.add_argument("--terms", action="store_true")
+    ap.add_argument("--token-sort", action="store_true")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("sim_probe: no GPU")
@@ -110,13 +118,44 @@ def main():
         st.synchronize()
         return e0.elapsed_time(e1)
 
+    raw2 = torch.zeros_like(raw)  # the token-sorted batch: the search keeps reading the queries as they are
+
+    def sort_alone():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        ix.token_sort_device(*args, raw2.data_ptr(), st.cuda_stream)
+        e1.record(st)
+        st.synchronize()
+        return e0.elapsed_time(e1)
+
+    def search_sorted_rerank(metric):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ix.search_device(*args, a.threshold, a.limit, stride, *outs, st.cuda_stream)
+        e0.record(st)
+        ix.token_sort_device(*args, raw2.data_ptr(), st.cuda_stream)
+        ix.rerank_device(raw2.data_ptr(), off.data_ptr(), nq, stride, *outs, dv.data_ptr(), a.min_similarity,
+                         st.cuda_stream, metric=metric, d_terms=d_terms, token_sort=True)
+        e1.record(st)
+        st.synchronize()
+        return e0.elapsed_time(e1)
+
+    flagged = ["levenshtein"] + [mt for mt in a.metric if mt != "levenshtein"] if a.token_sort else []
+    build_ms = None
+    if a.token_sort:  # the first flagged call on the replica builds its token-sorted terms (no records yet: dn is zero)
+        t = time.perf_counter()
+        ix.similarity_device(*args, stride, dn.data_ptr(), dk.data_ptr(), dv.data_ptr(), st.cuda_stream, token_sort=True)
+        st.synchronize()
+        build_ms = (time.perf_counter() - t) * 1e3
     for _ in range(a.warmup):
         search()
         search_rerank()
         for mt in a.metric:
             search_rerank(mt)
+        for mt in flagged:
+            search_sorted_rerank(mt)
     t_search, t_both, t_stage, t_sim = [], [], [], []
     m_stage, m_sim = {mt: [] for mt in a.metric}, {mt: [] for mt in a.metric}
+    f_stage, t_sort = {mt: [] for mt in flagged}, []
     for _ in range(a.reps):
         t_search.append(search())
         # the search's answer as the stage finds it: records, term characters, bytes its gathers touch
@@ -140,10 +179,24 @@ def main():
         t_stage.append(stage)
         for mt in a.metric:
             m_stage[mt].append(search_rerank(mt)[1])
+        for mt in flagged:
+            f_stage[mt].append(search_sorted_rerank(mt))
+        if a.token_sort:
+            t_sort.append(sort_alone())
     kept = int(dn.cpu().numpy().astype(np.int64).sum())
     m = [len(sim_ref.normalise(q)) for q in queries]
     long_q = np.array([x > 64 for x in m])
     ms, mb, mg, mv = (statistics.median(x) for x in (t_search, t_both, t_stage, t_sim))
+    token = None
+    if a.token_sort:
+        plain = {"levenshtein": mg, **{mt: statistics.median(m_stage[mt]) for mt in a.metric}}
+        terms = {sim_ref.normalise(w) for w in words}
+        ts_chars = sum(len(token_ref.sorted_term(t)) for t in terms)
+        token = {"token_sort_kernel_ms": spread(t_sort), "query_bytes": int(offs[-1]),
+                 "first_flagged_call_ms": round(build_ms, 3), "sorted_term_bytes": ts_chars + 8 + 8 * (len(terms) + 1),
+                 "flagged": {mt: {"rerank_stage_ms": spread(f_stage[mt]),
+                                  "ratio_to_unflagged": round(statistics.median(f_stage[mt]) / plain[mt], 4)}
+                             for mt in flagged}}
     print(json.dumps({
         "rows": a.rows, "queries": nq, "threshold": a.threshold, "limit": a.limit, "min_similarity": a.min_similarity,
         "reps": a.reps, "warmup": a.warmup,
@@ -155,6 +208,7 @@ def main():
         "terms": a.terms,
         "metrics": {mt: {"rerank_stage_ms": spread(m_stage[mt]), "similarity_kernel_ms": spread(m_sim[mt]),
                          "stage_ratio": round(statistics.median(m_stage[mt]) / mg, 4)} for mt in a.metric},
+        **({"token_sort": token} if token else {}),
         "gather_bytes": gather_bytes, "gather_GBps_similarity": round(gather_bytes / (mv * 1e-3) / 1e9, 2),
         "version": _native.lib().ngsVersion().decode()}))
     ix.dispose()
