@@ -511,6 +511,82 @@ NGS_API int64_t ngsTerm(uint32_t handle, uint32_t termId, void* buf, uint64_t ca
 NGS_API int ngsTokenSortDevice(uint32_t handle, const uint8_t* dBytes, const uint64_t* dOffsets, uint32_t n,
                                uint8_t* dOut, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Linking two indexes: which key of a target index T each key of a source index S corresponds to
+ * (not in the reference). nS and nT are their ngsNumKeys.
+ *
+ * Candidate row. The row of source key a is the answer ngsSearchDevice on T gives at (threshold,
+ * limit) for the string of key a of S, as ngsKey / ngsKeyW returns it without its NUL, normalised
+ * with T's current validChar set like any query. No record is dropped: S and T may be one handle, and
+ * then a key may find itself. limit is 1..4,096 and Ls = min(limit, nT) is the row stride.
+ *
+ * Similarity filter. With minSimilarity > -1.0f a record is kept unless its similarity is below
+ * minSimilarity, in the search's order (dedupKeysM's filter). The similarity is
+ * ngsSimilarityDeviceM's on T by `metric`: the query is S's key string, the terms are T's. With
+ * NGS_SIM_TOKEN_SORT the batch is token-sorted in place behind the search.
+ *
+ * Value and edge order. The value of a record is its similarity when the filter is on and its score
+ * when it is off. An edge is (a, b, value). Edges are totally ordered by value descending, then a
+ * ascending, then b ascending; values compare by the order image of their fp32 bits (bits with the
+ * sign bit set inverted, the others with the sign bit set): numeric order for non-NaN floats, with
+ * -0 < +0, and a NaN where its bits put it.
+ *
+ * Modes. NGS_LINK_BEST: match[a] is the b of a's first edge in that order, NGS_NO_MATCH for an empty
+ * row; many a may share a b. NGS_LINK_ONE_TO_ONE: the greedy matching: go through all edges in that
+ * order and take an edge iff both its ends are still free; match[a] is the b taken for a, or
+ * NGS_NO_MATCH. The result is unique: it does not depend on batches, scheduling or replicas.
+ *
+ * The device composition: ngsKeyQueriesDevice on S, ngsSearchDevice on T (and, for a filter,
+ * ngsSimilarityDeviceM on T), then ngsMatchDevice over the block, all on one stream and one device.
+ * ------------------------------------------------------------------------------------ */
+#define NGS_NO_MATCH 0xFFFFFFFFu
+
+/* The greedy one-to-one matching of a block in rounds. The block has ngsSearchDevice's layout; its
+ * edges are (firstKey + i, dKeys[i * stride + r], dValues[i * stride + r]) for r < min(dCounts[i],
+ * stride); dValues is the caller's choice, dScores or dSim. An edge with a >= nA or b >= nB is
+ * ignored, and nothing is read through that id. dMatchA[nA] and dMatchB[nB] are the matching from
+ * both sides (dMatchA[a] = b and dMatchB[b] = a, NGS_NO_MATCH for a free end), dBids[nB] is scratch,
+ * *dMatched the number of pairs. The flags of one call run in the order INIT, BEGIN, BID, ACCEPT.
+ *
+ * An edge is live when both its ends are unmatched. A round is BEGIN, then BID over every block, then
+ * ACCEPT over every block: BID makes dBids[b] the largest live edge at b, ACCEPT lets every unmatched
+ * row take its own largest live edge if dBids names that same edge, and adds the pairs to *dMatched.
+ * A caller with one block passes BEGIN | BID | ACCEPT, plus INIT the first time; a caller with
+ * several passes BEGIN | BID on the first block, BID on the others, then ACCEPT on each. A row
+ * (a value of firstKey + i) belongs to one block. The matching is complete after the first round
+ * that adds nothing to *dMatched: read the word between rounds. Every round with live edges matches
+ * at least one pair, a round on a complete matching changes nothing, and the result is exactly the
+ * greedy matching above whatever order the rows run in. Stream-ordered, no host wait.
+ * 0; -3 an unknown flag, NULL dMatched, NULL dMatchA with nA non-zero, NULL dMatchB or dBids with nB
+ * non-zero, NULL dCounts, dKeys or dValues with n and stride non-zero and BID or ACCEPT set; -4 HIP
+ * error. n = 0 with flags is valid. */
+#define NGS_MATCH_INIT 1u   /* dMatchA[0..nA) = dMatchB[0..nB) = NGS_NO_MATCH, *dMatched = 0 */
+#define NGS_MATCH_BEGIN 2u  /* a round starts: the bids are cleared */
+#define NGS_MATCH_BID 4u    /* the block's live edges bid for their b */
+#define NGS_MATCH_ACCEPT 8u /* the block's rows take the edges that won at both ends */
+NGS_API int ngsMatchDevice(const uint32_t* dCounts, const uint32_t* dKeys, const float* dValues, uint32_t n,
+                           uint32_t stride, uint32_t firstKey, uint32_t* dMatchA, uint32_t nA, uint32_t* dMatchB,
+                           uint32_t nB, uint64_t* dBids, uint32_t* dMatched, uint32_t flags, void* stream);
+
+/* Links the keys of hFrom (S) to the keys of hTo (T) as defined above: match[nS] (caller-allocated),
+ * and for the chosen record of each source key scores[nS] and sims[nS] (each may be NULL): 0.0f and
+ * -1.0f for an unmatched key, sims all -1.0f when the filter is off (nothing was computed). Returns
+ * the number of matched source keys. T's first replica answers, and S must have a replica on that
+ * device. batchKeys: source keys per batch (0 = 65,536). NGS_LINK_BEST holds one batch's block on
+ * the device; NGS_LINK_ONE_TO_ONE holds the whole block of nS x Ls records (keys, scores, and
+ * similarities with a filter: 8 or 12 bytes a record) and runs rounds over it until one adds
+ * nothing. Everything is read back once, at the end.
+ * On failure it returns 0 and sets ngsLastError; match, scores and sims are untouched. A HIP
+ * invalid-value code: NULL match, limit 0, a NaN minSimilarity, an unknown metric or mode, an unknown
+ * or un-built hFrom or hTo, ngsCharSize differing between the two, no replica of S on T's device.
+ * NGS_ERR_RERANK_LIMIT: limit above 4,096. The arguments are checked before the handles. nS = 0
+ * returns 0 without an error. */
+#define NGS_LINK_BEST 0u
+#define NGS_LINK_ONE_TO_ONE 1u
+NGS_API uint32_t linkKeys(uint32_t hFrom, uint32_t hTo, float threshold, uint32_t limit, uint32_t metric,
+                          float minSimilarity, uint32_t mode, uint32_t batchKeys, uint32_t* match, float* scores,
+                          float* sims);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);

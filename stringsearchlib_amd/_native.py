@@ -153,6 +153,9 @@ EXPORTS = [
                            "ngsClusterDevice": (ci, [vp, vp, u32, u32, u32, vp, u32, u32, vp]),
                            "selfJoin": (u32, [u32, u32, u32, f32, u32, u32, PU, PU, P(f32)]),
                            "dedupKeys": (u32, [u32, f32, u32, f32, u32, PU])}),
+    # linking two indexes
+    ("ngsMatchDevice", {"ngsMatchDevice": (ci, [vp, vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, vp, u32, vp]),
+                        "linkKeys": (u32, [u32, u32, f32, u32, u32, f32, u32, u32, PU, P(f32), P(f32)])}),
     ("ngsServeState", {"ngsServeState": (ci, [u32])}),
     ("ngsLastError", {"ngsLastError": (ci, [ci])}),
     ("ngsReplicaDigest", {"ngsReplicaDigest": (ci, [u32, ci, P(u64), ci])}),

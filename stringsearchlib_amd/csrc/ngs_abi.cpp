@@ -29,6 +29,7 @@
 #include "ngs_index.h"
 #include "ngs_join.h"
 #include "ngs_kernels.h"
+#include "ngs_match.h"
 #include "ngs_sim.h"
 #include "ngs_token.h"
 #include "ngs_utf8.h"
@@ -2851,6 +2852,107 @@ uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric,
     return clusters;
 }
 
+// ---- linking two indexes (linkKeys) ----
+constexpr uint32_t kLinkRoundsPerRead = 4;  // rounds queued between two reads of the pair count
+
+// linkKeys: the keys of S searched in T a batch at a time (gathered on S's replica, searched and
+// measured on T's first one, both on one device), then per source key the best target (kLinkBest, a
+// batch's block at a time) or the greedy one-to-one matching over the whole block kept on the device
+// (kLinkOneToOne, in rounds). The match, the chosen records' scores and similarities are read back once.
+uint32_t link_host(uint32_t h_from, uint32_t h_to, float thr, uint32_t limit, uint32_t metric, float min_sim,
+                   uint32_t mode, uint32_t batch_keys, uint32_t* match, float* scores, float* sims) {
+    if (!match || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim || !sim_metric_ok(metric) ||
+        mode >= kLinkModes) {
+        t_last_error = match && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
+        return 0;
+    }
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* S = find_lib(h_from);
+    Library* T = find_lib(h_to);
+    if (!S || !T || !S->host.indexed || !T->host.indexed || S->host.csize != T->host.csize) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    Replica& R = *T->reps.front();
+    Replica* RS = S->replica_at(R.device);
+    if (!RS) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    const uint32_t nS = S->host.n_keys, nT = T->host.n_keys;
+    if (nS == 0) return 0;
+    BatchGuard bg_to(T), bg_from(S == T ? nullptr : S);
+    if (!HIP_CHECK(hipSetDevice(R.device))) return 0;
+    const uint32_t Ls = std::max(effective_limit(*T, limit), 1u);  // (a target without keys: empty rows of one cell)
+    const uint32_t B = join_batch_keys(batch_keys, nS, Ls);
+    const bool verify = min_sim > -1.0f;  // every similarity is >= -1: nothing to filter at or below it
+    const bool whole = mode == kLinkOneToOne;
+    const uint32_t rows = whole ? nS : B;  // the block kept: every batch's, or one batch's
+    CallScratch M;
+    uint32_t *d_match = nullptr, *d_match_b = nullptr, *d_matched = nullptr;
+    uint64_t* d_bids = nullptr;
+    float *d_v = nullptr, *d_os = nullptr, *d_ov = nullptr;
+    if (!M.begin(rows, Ls, join_max_query_bytes(*S, 0, nS, B)) || !M.alloc(&d_match, nS) || !M.alloc(&d_matched, 1) ||
+        !M.alloc(&d_os, nS) || !M.alloc(&d_ov, nS) || (verify && !M.alloc(&d_v, (size_t)rows * Ls)) ||
+        (whole && (!M.alloc(&d_match_b, nT) || !M.alloc(&d_bids, nT))))
+        return 0;
+    if (!whole && !HIP_CHECK(hipMemsetAsync(d_matched, 0, sizeof(uint32_t), M.stream))) return 0;
+    for (uint32_t done = 0; done < nS; done += B) {
+        const uint32_t n = std::min(B, nS - done);
+        const size_t at = whole ? (size_t)done : 0;
+        uint32_t *d_n = M.d_n + at, *d_k = M.d_k + at * Ls;
+        float *d_s = M.d_s + at * Ls, *d_sim = verify ? d_v + at * Ls : nullptr;
+        if (!HIP_CHECK(launch_key_queries(RS->dev, done, n, join_query_bytes(*S, done, n), M.d_raw, M.d_off, M.stream)))
+            return 0;
+        if (search_on_replica(*T, R, M.d_raw, M.d_off, n, thr, effective_limit(*T, limit), Ls, d_n, d_k, d_s,
+                              M.stream) != 0) {
+            if (!t_last_error) t_last_error = kErrInternal;
+            return 0;
+        }
+        if (verify && (queue_similarity(*T, R, M.d_raw, M.d_off, n, Ls, d_n, d_k, d_s, d_sim, nullptr, metric, false,
+                                        0.0f, M.stream, M.d_raw) != 0 ||
+                       !HIP_CHECK(launch_keep_similar(d_n, d_k, d_s, d_sim, n, Ls, min_sim, M.stream, d_sim))))
+            return 0;
+        if (!whole && (!HIP_CHECK(launch_match_best(d_n, d_k, verify ? d_sim : d_s, n, Ls, done, d_match, nS, nT,
+                                                    d_matched, M.stream)) ||
+                       !HIP_CHECK(launch_match_gather(d_n, d_k, d_s, d_sim, n, Ls, done, d_match, nS, d_os, d_ov,
+                                                      M.stream))))
+            return 0;
+    }
+    uint32_t matched = 0;
+    auto read_matched = [&](uint32_t& out) {
+        return HIP_CHECK(hipMemcpyAsync(&out, d_matched, sizeof(uint32_t), hipMemcpyDeviceToHost, M.stream)) &&
+               HIP_CHECK(hipStreamSynchronize(M.stream));
+    };
+    if (whole) {
+        // rounds until one adds nothing: a round on a complete matching changes nothing, so a few are
+        // queued per read of the count
+        const float* d_val = verify ? d_v : M.d_s;
+        uint32_t flags = kMatchFlags;  // INIT with the first round
+        for (uint32_t before = kNoMatch; matched != before;) {
+            before = matched;
+            for (uint32_t r = 0; r < kLinkRoundsPerRead; ++r, flags &= ~kMatchInit)
+                if (!HIP_CHECK(launch_match(M.d_n, M.d_k, d_val, nS, Ls, 0, d_match, nS, d_match_b, nT, d_bids,
+                                            d_matched, flags, M.stream)))
+                    return 0;
+            if (!read_matched(matched)) return 0;
+        }
+        if (!HIP_CHECK(launch_match_gather(M.d_n, M.d_k, M.d_s, d_v, nS, Ls, 0, d_match, nS, d_os, d_ov, M.stream)))
+            return 0;
+    }
+    std::vector<uint32_t> h_match(nS);
+    std::vector<float> h_os(scores ? nS : 0), h_ov(sims ? nS : 0);
+    if (!HIP_CHECK(hipMemcpyAsync(h_match.data(), d_match, sizeof(uint32_t) * nS, hipMemcpyDeviceToHost, M.stream)) ||
+        (scores && !HIP_CHECK(hipMemcpyAsync(h_os.data(), d_os, sizeof(float) * nS, hipMemcpyDeviceToHost, M.stream))) ||
+        (sims && !HIP_CHECK(hipMemcpyAsync(h_ov.data(), d_ov, sizeof(float) * nS, hipMemcpyDeviceToHost, M.stream))) ||
+        !read_matched(matched))
+        return 0;
+    std::copy(h_match.begin(), h_match.end(), match);
+    if (scores) std::copy(h_os.begin(), h_os.end(), scores);
+    if (sims) std::copy(h_ov.begin(), h_ov.end(), sims);
+    return matched;
+}
+
 // A scan's scratch: one grow-only buffer per (device, stream), 64 KiB at first, so that calls on
 // different streams never share one while their scans run; a buffer is replaced only after its
 // stream's earlier work has finished with it. The caller holds mu from get() until its kernels are
@@ -3484,6 +3586,24 @@ NGS_API uint32_t dedupKeys(uint32_t handle, float threshold, uint32_t limit, flo
 NGS_API uint32_t dedupKeysM(uint32_t handle, float threshold, uint32_t limit, uint32_t metric, float minSimilarity,
                             uint32_t batchKeys, uint32_t* labels) {
     return dedup_host(handle, threshold, limit, metric, minSimilarity, batchKeys, labels);
+}
+
+NGS_API int ngsMatchDevice(const uint32_t* dCounts, const uint32_t* dKeys, const float* dValues, uint32_t n,
+                           uint32_t stride, uint32_t firstKey, uint32_t* dMatchA, uint32_t nA, uint32_t* dMatchB,
+                           uint32_t nB, uint64_t* dBids, uint32_t* dMatched, uint32_t flags, void* stream) {
+    if ((flags & ~kMatchFlags) || !dMatched || (nA && !dMatchA) || (nB && (!dMatchB || !dBids)) ||
+        (n && stride && (flags & (kMatchBid | kMatchAccept)) && (!dCounts || !dKeys || !dValues)))
+        return -3;
+    return HIP_CHECK(launch_match(dCounts, dKeys, dValues, n, stride, firstKey, dMatchA, nA, dMatchB, nB, dBids,
+                                  dMatched, flags, (hipStream_t)stream))
+               ? 0
+               : -4;
+}
+
+NGS_API uint32_t linkKeys(uint32_t hFrom, uint32_t hTo, float threshold, uint32_t limit, uint32_t metric,
+                          float minSimilarity, uint32_t mode, uint32_t batchKeys, uint32_t* match, float* scores,
+                          float* sims) {
+    return link_host(hFrom, hTo, threshold, limit, metric, minSimilarity, mode, batchKeys, match, scores, sims);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

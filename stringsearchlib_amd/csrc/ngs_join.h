@@ -107,9 +107,10 @@ hipError_t launch_key_queries(const DevIndex& X, uint32_t first, uint32_t n, uin
                               uint64_t* off, hipStream_t s);
 hipError_t launch_drop_self(uint32_t* counts, uint32_t* keys, float* scores, uint32_t n, uint32_t stride,
                             uint32_t first, uint32_t limit, hipStream_t s);
-// records with sim < min_sim removed from every row, the others kept in order (keys and scores)
+// records with sim < min_sim removed from every row, the others kept in order (keys and scores; with
+// sim_out = sim their similarities too, so that sim stays in the records' layout)
 hipError_t launch_keep_similar(uint32_t* counts, uint32_t* keys, float* scores, const float* sim, uint32_t n,
-                               uint32_t stride, float min_sim, hipStream_t s);
+                               uint32_t stride, float min_sim, hipStream_t s, float* sim_out = nullptr);
 hipError_t launch_cluster(const uint32_t* counts, const uint32_t* keys, uint32_t n, uint32_t stride, uint32_t first,
                           uint32_t* labels, uint32_t n_labels, uint32_t flags, hipStream_t s);
 #endif

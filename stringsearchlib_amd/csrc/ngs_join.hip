@@ -141,9 +141,11 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void k_drop_self(uint32_t* coun
 
 // the records with sim >= min_sim, in order (what ngsRerankDevice keeps, without its sort and
 // without its cap on the stride: a join row's stride is one more than the limit)
+// (kMoveSim: the similarities move with their records, in place; sim is then written too)
+template <bool kMoveSim>
 __global__ __launch_bounds__(64 * kRowsPerBlock) void k_keep_similar(uint32_t* counts, uint32_t* keys, float* scores,
-                                                                    const float* sim, uint32_t n, uint32_t stride,
-                                                                    float min_sim) {
+                                                                    const float* sim, float* sim_out, uint32_t n,
+                                                                    uint32_t stride, float min_sim) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t row = (uint64_t)blockIdx.x * kRowsPerBlock + (threadIdx.x >> 6);
     if (row >= n) return;
@@ -157,13 +159,15 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void k_keep_similar(uint32_t* c
         const bool live = r < count;
         const uint32_t rk = live ? k[r] : 0u;
         const float rs = live ? sc[r] : 0.0f;
-        const bool keep = live && !(sv[r] < min_sim);
+        const float rv = live ? sv[r] : 0.0f;
+        const bool keep = live && !(rv < min_sim);
         const uint64_t bal = __ballot(keep);
         const uint32_t at = kept + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
         __builtin_amdgcn_s_waitcnt(0);
         if (keep) {
             k[at] = rk;
             sc[at] = rs;
+            if (kMoveSim) sim_out[row * stride + at] = rv;
         }
         kept += (uint32_t)__popcll(bal);
     }
@@ -267,10 +271,14 @@ hipError_t launch_drop_self(uint32_t* counts, uint32_t* keys, float* scores, uin
 }
 
 hipError_t launch_keep_similar(uint32_t* counts, uint32_t* keys, float* scores, const float* sim, uint32_t n,
-                               uint32_t stride, float min_sim, hipStream_t s) {
+                               uint32_t stride, float min_sim, hipStream_t s, float* sim_out) {
     if (!n) return hipSuccess;
-    hipLaunchKernelGGL(k_keep_similar, dim3((n + kRowsPerBlock - 1u) / kRowsPerBlock), dim3(64 * kRowsPerBlock), 0, s,
-                       counts, keys, scores, sim, n, stride, min_sim);
+    const dim3 grid((n + kRowsPerBlock - 1u) / kRowsPerBlock), block(64 * kRowsPerBlock);
+    if (sim_out)
+        hipLaunchKernelGGL(k_keep_similar<true>, grid, block, 0, s, counts, keys, scores, sim, sim_out, n, stride, min_sim);
+    else
+        hipLaunchKernelGGL(k_keep_similar<false>, grid, block, 0, s, counts, keys, scores, sim, sim_out, n, stride,
+                           min_sim);
     return hipGetLastError();
 }
 

@@ -30,6 +30,7 @@ NGS_ERR_RERANK_LIMIT = 0x10003
 METRICS = {"levenshtein": 0, "osa": 1, "partial": 2}
 TOKEN_SORT = 0x100  # NGS_SIM_TOKEN_SORT: OR'ed onto a metric
 NO_TERM = 0xFFFFFFFF
+NO_MATCH = 0xFFFFFFFF  # NGS_NO_MATCH: link() found no key for this one
 
 
 def _metric(metric, token_sort: bool = False) -> int:
@@ -466,6 +467,50 @@ class StringIndex:
         _ok(_native.lib().ngsClusterDevice(d_counts or None, d_keys or None, n, stride, first, d_labels or None,
                                            n_labels, (1 if init else 0) | (2 if finish else 0), stream or None),
             "ngsClusterDevice")
+
+    # -- linking two indexes (include/ngram_search.h) -----------------------------------------
+    def link(self, other, threshold: float, limit: int = 10, min_similarity: float | None = None,
+             metric="levenshtein", token_sort: bool = False, one_to_one: bool = True, batch_keys: int = 0):
+        """linkKeys: every key of this index searched in `other` (same character width) at (threshold,
+        limit), limit in 1..4,096. Returns numpy arrays (match, scores, sims) over this index's keys:
+        match[a] = the key id of `other` linked to key a, or NO_MATCH; scores[a] and sims[a] those of
+        the chosen record (0.0 and -1.0 for an unmatched key). With min_similarity only the records
+        whose similarity by `metric` (token_sort: of the token-sorted strings) is at least that count,
+        and they are ranked by it; without it they are ranked by score and sims is None.
+        one_to_one: the greedy matching (the best record overall first; no key of `other` is given
+        twice); otherwise every key takes its best record."""
+        import numpy as np
+        L = _native.lib()
+        if L.ngsCharSize(self.handle) != L.ngsCharSize(other.handle):
+            raise ValueError("link: the two indexes differ in character width")
+        n = self.num_keys()
+        match = np.full(max(1, n), NO_MATCH, dtype=np.uint32)
+        scores = np.zeros(max(1, n), dtype=np.float32)
+        sims = np.full(max(1, n), -1.0, dtype=np.float32)
+        ms = -1.0 if min_similarity is None else min_similarity
+        L.ngsLastError(1)
+        matched = L.linkKeys(self.handle, other.handle, threshold, limit, _metric(metric, token_sort), ms,
+                             1 if one_to_one else 0, batch_keys, match.ctypes.data_as(C.POINTER(C.c_uint32)),
+                             scores.ctypes.data_as(C.POINTER(C.c_float)), sims.ctypes.data_as(C.POINTER(C.c_float)))
+        if not matched:
+            _check("linkKeys")
+        match, scores, sims = match[:n], scores[:n], sims[:n]
+        assert matched == int((match != NO_MATCH).sum())
+        return match, scores, (sims if min_similarity is not None and ms > -1.0 else None)
+
+    @staticmethod
+    def match_device(d_counts: int, d_keys: int, d_values: int, n: int, stride: int, first: int, d_match_a: int,
+                     n_a: int, d_match_b: int, n_b: int, d_bids: int, d_matched: int, init: bool = False,
+                     begin: bool = True, bid: bool = True, accept: bool = True, stream: int = 0) -> None:
+        """ngsMatchDevice on raw device pointers: one step of the greedy one-to-one matching over the block's
+        (first + i, key, value) records. `init` frees every end and zeroes the pair count, `begin` starts a
+        round (the bids cleared), `bid` lets the block's live records bid, `accept` takes the records that
+        won at both ends and adds them to the count at d_matched. A round over one block is the default
+        flags; repeat until the count stops growing. Queued on `stream`."""
+        flags = (1 if init else 0) | (2 if begin else 0) | (4 if bid else 0) | (8 if accept else 0)
+        _ok(_native.lib().ngsMatchDevice(d_counts or None, d_keys or None, d_values or None, n, stride, first,
+                                         d_match_a or None, n_a, d_match_b or None, n_b, d_bids or None,
+                                         d_matched or None, flags, stream or None), "ngsMatchDevice")
 
     def search_device_async(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int,
                             out_stride: int, d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> int:
