@@ -14,7 +14,9 @@ The corpora sit at the build's edges: word counts around the 256-thread blocks, 
 without skipped words; short last rows; one valid word; one term or key shared by every row;
 keys equal only after trimming; keys whose first row yields no pair; 2g - 1 and 2g characters
 for every gram size; signed, subnormal, infinite and NaN weights; libraries without any pair;
-code points up to 0x10FFFF and values above; one and several skip buckets in both gram modes.
+code points up to 0x10FFFF and values above; one and several skip buckets in both gram modes;
+different strings of one 64-bit interner hash among the terms, the keys or both, where the device
+build defers to the host build (tests/hash_cases.py).
 """
 import ctypes as C
 import os
@@ -23,6 +25,7 @@ import random
 import pytest
 
 import build_ref
+import hash_cases
 import index_file
 import stringsearchlib_amd as ssl
 from stringsearchlib_amd import _native
@@ -247,6 +250,13 @@ def _():
 def _():
     rng = random.Random(3)  # four letters: every list is long, so the bucket count follows the lists
     return [bytes(rng.choice(b"ACGT") for _ in range(rng.randint(6, 14))) for _ in range(700)], 1, None
+
+
+# two different strings of one 64-bit interner hash in one run (tests/hash_cases.py): the device build
+# defers to the host build, and every array is still the model's (tests/test_gpu_intern_collision.py
+# shows that it deferred)
+for _name in hash_cases.DEFERRING:
+    corpus(_name, [W2, W3])(lambda n=_name: hash_cases.collision_corpora()[n])
 
 
 CASES = [(name, shape) for name, (_, shapes, _) in CORPORA.items() for shape in shapes]
