@@ -134,7 +134,8 @@ constexpr int kWaveTarget = kWaveCap * 5 / 8;   // postings per exact part the b
 #define NGS_TGT8 5
 #endif
 constexpr int kSketchTarget = kSketchCap * NGS_TGT8 / 8;  // ... per sketch part (bucket groups aim at NGS_TGT8/8 of the cap)
-constexpr int kGroupTarget = kSketchCap * NGS_TGT8 / 8;  // ... the same for tier 1a's lane-group staging (lean_query_g)
+constexpr int kGroupTarget = kSketchCap * NGS_TGT8 / 8;  // ... the same for tier 1a's lane-group staging (lean_query_g): its widest part
+constexpr uint32_t kMaxPartWidth = 8;           // ... whose parts are up to this many steps of buckets, as many as fit (group_quota, below)
 constexpr uint32_t kStray = 0xFFFFFFFFu;        // staged entry outside its list segment
 constexpr int kWaveSurv = 128;                  // survivor list (term, count) before calcScore
 constexpr uint32_t kEmitCap = 1024;
@@ -272,6 +273,48 @@ __host__ __device__ inline uint32_t heavy_slices(const SearchParams& P, uint32_t
     if (want > kHeavyMaxSlices) want = kHeavyMaxSlices;
     if (want > X.n_buckets) want = X.n_buckets;
     return want ? want : 1u;
+}
+
+// Lane groups of the main tier-1a launch (lean_query_g): the wave's 64 lanes apportioned to a
+// query's ng <= 64 non-empty lists in proportion to their lengths, every list at least one lane,
+// every lane given out. List j's exact share of the 64 - ng lanes past the first of each list is
+// (64 - ng) len_j / P; it gets the floor of that, and the lanes the floors leave over go one each
+// to the lists of the largest remainders (ties to the lower list). So no list's postings per lane
+// exceed P / (64 - ng), and near-equal lists differ by one lane at most.
+// group_share: list j's share in 2^-kShareBits lanes (len_j <= P < 2^38, so the product fits);
+// group_quota: its lanes, from the share, the lanes left over (64 - ng - the sum of the floors)
+// and the other lists' shares (share_of(k), k < ng: an array on the host, a readlane on the device)
+constexpr uint32_t kShareBits = 20;
+__host__ __device__ inline uint64_t group_share(uint32_t ng, uint32_t len, uint64_t p_total) {
+    return (((uint64_t)(64u - ng) * len) << kShareBits) / (p_total ? p_total : 1u);
+}
+// the order of the remainders: the fraction, then the lower list first (distinct for distinct j)
+__host__ __device__ inline uint32_t group_rem_key(uint64_t share, uint32_t j) {
+    return (((uint32_t)share & ((1u << kShareBits) - 1u)) << 6) | (63u - j);
+}
+template <class KeyOf>
+__host__ __device__ inline uint32_t group_quota(uint32_t ng, uint32_t j, uint64_t share, uint32_t left, KeyOf key_of) {
+    const uint32_t key = group_rem_key(share, j);
+    uint32_t above = 0;  // lists whose remainder comes before this one's
+    for (uint32_t k = 0; k < ng; ++k) above += key_of(k) > key ? 1u : 0u;
+    return 1u + (uint32_t)(share >> kShareBits) + (above < left ? 1u : 0u);
+}
+
+// Part width of the main tier-1a launch: a part is the widest run of up to wmax buckets in which
+// every list's segment fits its lanes' register rounds. Entries [cur, e) of a list that starts a0
+// entries into a 16-byte chunk cover ((a0 + e + 3) >> 2) - ((a0 + cur) >> 2) chunks; that is at
+// most capc exactly when e <= part_entry_limit (and an empty segment, e == cur, always is)
+__host__ __device__ inline uint32_t part_entry_limit(uint32_t a0, uint32_t cur, uint32_t capc) {
+    return 4u * (capc + ((a0 + cur) >> 2)) - a0;
+}
+// ... in steps of 2^part_step_shift buckets: one bucket, unless the part target is wtgt buckets wide
+// and the wmax widths a query's smallest group can try would stop short of half of it (a query of a
+// few postings: its widest part is then the target's width, within the wspan buckets a part may span)
+__host__ __device__ inline uint32_t part_step_shift(uint32_t wmax, uint32_t wspan, uint64_t wtgt) {
+    const uint32_t r = (uint32_t)(wtgt < wspan ? wtgt : wspan) / wmax;
+    uint32_t sh = 0;
+    while ((2u << sh) <= r) ++sh;
+    return sh;
 }
 
 // Tier 1b slices per query (SearchParams.nslices): a full-list or handed-over query is a few

@@ -2404,11 +2404,13 @@ __device__ __forceinline__ void lean_query(WaveSmem<true>& S, const uint32_t q, 
 }
 
 // Tier 1a with lane groups (the main launch): each of the query's lists owns a fixed group of lanes
-// for the whole query, sized in proportion to its length (quota_j = 1 + (64 - ng) * len_j / P lanes).
+// for the whole query, sized in proportion to its length; the groups take all 64 lanes (group_quota).
 // Lane `slot` of list j's group loads chunks slot, slot + G, slot + 2G of that list's segment in
 // each part, so a chunk never has to find its list: no per-part prefix sum, list-start map or
 // segment table, no LDS round trips before a load. A part fits when no list has more than
-// 3 G chunks (its lanes' three register rounds). The part's entry bounds are applied only where a
+// 3 G chunks (its lanes' three register rounds), and each part is as many whole buckets as fit: the
+// first lanes of a group hold the list's skip entries of the next buckets, one width each, and a
+// wave reduction finds the widest at which every list fits. The part's entry bounds are applied only where a
 // cell reached cmin (the sketch counts the <= 3 neighbouring entries at each segment edge, never an
 // undercount): entry e of chunk k is in the segment iff 4k + e - head < len.
 
@@ -2590,24 +2592,38 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
         if (lane == 0) atomicAdd(P.actr + 1, (uint32_t)more);
     };
     if (p_total && cmin <= n) {
-        // ---- lane groups: list j owns lanes [gend_j - gq_j, gend_j), gq_j = 1 + (64 - ng) len_j / P ----
-        const uint32_t quota = lane < ng ? 1u + (uint32_t)(((uint64_t)(64u - ng) * glen) / p_total) : 0u;
+        // ---- lane groups: list j owns lanes [gend_j - gq_j, gend_j); the gq_j (group_quota) are in
+        // proportion to the lists' lengths and sum to 64, so every lane has a list ----
+        const uint64_t share = lane < ng ? group_share(ng, glen, p_total) : 0u;
+        const uint32_t rkey = group_rem_key(share, lane);
+        const uint32_t left = 64u - ng - wave_sum_u32((uint32_t)(share >> kShareBits));
+        const uint32_t gq = group_quota(ng, lane, share, left, [&](uint32_t k) {
+            return (uint32_t)__builtin_amdgcn_readlane(rkey, k);
+        });
+        const uint32_t quota = lane < ng ? gq : 0u;
         const uint32_t qincl = wave_incl_scan(quota);
         uint32_t jl = 0;  // this lane's list: the lists whose groups end at or below it
         for (uint32_t k = 0; k < ng; ++k) jl += lane >= (uint32_t)__builtin_amdgcn_readlane(qincl, k) ? 1u : 0u;
-        const bool has = jl < ng;
-        const int js = (int)(has ? jl : 0u);
-        const uint32_t G = has ? (uint32_t)__shfl(quota, js) : 1u;  // the group's size
+        const int js = (int)min(jl, ng - 1u);  // (jl < ng: the last group ends at lane 64)
+        const uint32_t G = (uint32_t)__shfl(quota, js);  // the group's size
         const uint32_t k0 = lane - ((uint32_t)__shfl(qincl, js) - G);  // this lane's slot in it
         const uint64_t lbase = __shfl(gbase, js);
         const uint32_t lrow = (uint32_t)__shfl(grow, js);
         // cmin 2: every colliding pair is a false candidate, so those parts are cut at half the size
         const uint32_t shrink = cmin == 2 ? kLeanShrink2 : 0u;
         // chunks a part may hold of this lane's list: its lanes' three rounds (cut as the sketch part is)
-        const uint32_t capc = has ? min(3u * G, max(2u, (3u * G) >> shrink)) : 0u;
+        const uint32_t capc = min(3u * G, max(2u, (3u * G) >> shrink));
         const uint32_t K = X.n_buckets, span = X.bucket_span;
-        const uint32_t wmax = (uint32_t)max64(1, min64(K, kMaxPartSpan / max(span, 1u)));
-        const uint32_t w = (uint32_t)max64(1, min64(wmax, (uint64_t)K * (kGroupTarget >> shrink) / p_total));
+        // a part is 1 .. wmax steps of 2^ush buckets wide. wmax: the smallest group's lanes (lane k0 of
+        // a group holds the end of its list's segment at k0 + 1 steps), at most kMaxPartWidth, within
+        // the widest term-id span (wspan buckets). The step is one bucket unless the query's postings
+        // are so few that kGroupTarget of them take twice wmax buckets or more
+        const uint32_t gmin = 64u - (uint32_t)__builtin_amdgcn_readlane(wave_incl_max_scan(64u - G), 63);
+        const uint32_t wspan = (uint32_t)max64(1, min64(K, kMaxPartSpan / max(span, 1u)));
+        const uint32_t wmax = min(min(gmin, kMaxPartWidth), wspan);
+        const uint32_t ush = part_step_shift(wmax, wspan, (uint64_t)K * (kGroupTarget >> shrink) / p_total);
+        const uint32_t kw = min(k0, wmax - 1u);     // this lane's steps - 1 (lanes past wmax repeat the last)
+        const uint32_t gfirst4 = (lane - k0) << 2;  // the group's first lane, as a ds_bpermute address
         const uint32_t skrow = lrow * (K + 1);
         constexpr uint32_t b0 = 0;
         const uint32_t Kend = K;
@@ -2618,19 +2634,32 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
         const uint32_t cb = (uint32_t)(lbase >> 2);    // ... and its chunk (post holds < 2^34 entries)
         // entries [s, e) of this lane's list cover 16-byte chunks [(a0 + s) / 4, (a0 + e + 3) / 4)
         auto chunks = [a0](uint32_t s, uint32_t e) -> uint32_t { return e > s ? ((a0 + e + 3) >> 2) - ((a0 + s) >> 2) : 0u; };
-        // end of the next bucket group: skip[row][min(K, bn + w)]; lanes without a list load nothing
-        auto next_end = [&](uint32_t bn) -> uint32_t { return X.skip[skrow + min(Kend, bn + w)]; };
+        // the ends of the next steps: lane k0 of a group holds skip[row][min(K, bn + (k0 + 1 << ush))], the
+        // end of its list's segment in a part of k0 + 1 steps (one load per lane, as a fixed width took)
+        auto next_end = [&](uint32_t bn) -> uint32_t { return X.skip[skrow + min(Kend, bn + ((kw + 1u) << ush))]; };
         // fill of the fullest list against its cap, in 1/256: sub-part steps aim at 3/4 of it
         auto fill = [&](uint32_t nc) -> uint32_t {
-            const uint32_t f = has ? (nc * 256u + capc - 1u) / capc : 0u;
+            const uint32_t f = (nc * 256u + capc - 1u) / capc;
             return max(1u, __builtin_amdgcn_readlane(wave_incl_max_scan(f), 63));
         };
         uint32_t cur = 0, bnext = b0;
-        if (b0) cur = has ? X.skip[skrow + b0] : 0u;
-        uint32_t e_pre = has ? next_end(b0) : 0u;
+        if (b0) cur = X.skip[skrow + b0];
+        uint32_t e_pre = next_end(b0);
         // the first skip-table read waited for here: the loop header then merges only the back
         // edge's pending loads (with this one pending the wait there was vmcnt(0) on every part)
         asm volatile("" ::"v"(e_pre));
+        // steps of the next part: the most, up to wmax, at which every list's segment fits its cap.
+        // The ends ascend along a group, so a lane whose end is past the limit bounds the width by its
+        // k0; the least such k0 comes from a max scan of kMaxPartWidth - k0. 0: one step alone is
+        // over a list's cap
+        auto width = [&]() -> uint32_t {
+            const uint32_t over = e_pre > part_entry_limit(a0, cur, capc) ? kMaxPartWidth - kw : 0u;
+            return min(wmax, kMaxPartWidth - (uint32_t)__builtin_amdgcn_readlane(wave_incl_max_scan(over), 63));
+        };
+        // ... and the end of this lane's list's segment at t >= 1 steps, from lane t - 1 of its group
+        auto end_at = [&](uint32_t t) -> uint32_t {
+            return (uint32_t)__builtin_amdgcn_ds_bpermute((int)(gfirst4 + ((t - 1u) << 2)), (int)e_pre);
+        };
         uint32_t in_sub = 0, sub_lo = 0, hi_lim = 0, sub_end = 0, sub_bnext = 0, step = 1;
         unsigned* err = &stats->errors;
         uint32_t guard = 0;
@@ -2639,14 +2668,17 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
             bool have_p = false;
             in_sub = __builtin_amdgcn_readfirstlane(in_sub);
             bnext = __builtin_amdgcn_readfirstlane(bnext);
-            if (!in_sub && bnext < Kend) {  // common case, straight-line: the next bucket group fits
-                const uint32_t e = has ? e_pre : cur;
-                nch = chunks(cur, e);
-                if (!__ballot(nch > capc) && __ballot(nch != 0)) {
-                    len = e - cur;
-                    bnext = min(Kend, bnext + w);
-                    if (has) e_pre = next_end(bnext);
-                    return true;
+            if (!in_sub && bnext < Kend) {  // common case, straight-line: whole buckets fit
+                const uint32_t t = width();
+                if (t) {
+                    const uint32_t e = end_at(t);
+                    nch = chunks(cur, e);
+                    if (__ballot(nch != 0)) {
+                        len = e - cur;
+                        bnext = min(Kend, bnext + (t << ush));
+                        e_pre = next_end(bnext);
+                        return true;
+                    }
                 }
             }
             for (;;) {
@@ -2660,16 +2692,17 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
                 }
                 if (!in_sub) {
                     if (bnext >= Kend) break;
-                    const uint32_t bhi = min(Kend, bnext + w), e = has ? e_pre : cur;
+                    const uint32_t t = width(), e = end_at(max(t, 1u));
                     nch = chunks(cur, e);
-                    if (!__ballot(nch > capc)) {
+                    if (t) {
                         len = e - cur;
-                        bnext = bhi;
-                        if (has) e_pre = next_end(bnext);
+                        bnext = min(Kend, bnext + (t << ush));
+                        e_pre = next_end(bnext);
                         if (__ballot(nch != 0)) { have_p = true; break; }
                         continue;
                     }
-                    in_sub = 1;  // the group is over a list's cap: term-id sub-ranges of it
+                    in_sub = 1;  // the step is over a list's cap: term-id sub-ranges of it
+                    const uint32_t bhi = min(Kend, bnext + (1u << ush));
                     sub_lo = bnext * span;
                     hi_lim = (uint32_t)min64((uint64_t)bhi * span, n_long);
                     sub_end = e;
@@ -2678,7 +2711,7 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
                 }
                 const uint32_t hi = (uint32_t)min64(hi_lim, (uint64_t)sub_lo + step);
                 // lower_bound(list, hi) per lane, as a ballot-controlled (uniform) loop
-                uint32_t a = cur, b = has ? sub_end : cur;
+                uint32_t a = cur, b = sub_end;
                 while (__ballot(a < b)) {
                     const bool act = a < b;
                     const uint32_t mid = (a + b) >> 1;
@@ -2688,17 +2721,17 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
                     a = act && below ? mid + 1 : a;
                     b = act && !below ? mid : b;
                 }
-                nch = has ? chunks(cur, a) : 0u;
+                nch = chunks(cur, a);
                 if (__ballot(nch > capc) && hi - sub_lo > 1) {
                     step = max(1u, (uint32_t)((uint64_t)(hi - sub_lo) * 192u / fill(nch)));
                     continue;
                 }
-                len = has ? a - cur : 0u;
+                len = a - cur;
                 sub_lo = hi;
                 if (sub_lo >= hi_lim) {
                     in_sub = 0;
                     bnext = sub_bnext;
-                    if (has) e_pre = next_end(bnext);
+                    e_pre = next_end(bnext);
                 }
                 if (__ballot(nch != 0)) { have_p = true; break; }
                 cur = a;
@@ -2730,7 +2763,7 @@ __device__ __forceinline__ void lean_query_g(WaveSmem<true>& S, const uint32_t q
                 if (!__builtin_amdgcn_readfirstlane(spill() ? 1u : 0u)) {  // (uniform: no exec-masked exit)
                     slot_full();
                     // (DPP sum: a shuffle sum's lane-index vectors would be hoisted out of the part loop)
-                    arena_need(wave_sum_u32(has && k0 == 0 ? cur : 0u));
+                    arena_need(wave_sum_u32(k0 == 0 ? cur : 0u));
                     return false;
                 }
                 wave_sync();  // the list is read before it is refilled
