@@ -305,6 +305,9 @@ struct Context {
     // and the path counts, k_lists the list counters after reading them; false until a call has
     // queued both, and after a call that flagged *oflow
     bool stats_clean = false;
+    // the latency path's block (d_sio): the statistics slots the context's last small batch added to,
+    // which the next one's k_prep has to zero beside its own
+    uint32_t sio_slots = 0;
     hipEvent_t ev[6] = {};
     hipEvent_t piece_ev[kBackPieces] = {};  // finish_host_chunk: the read-back's pieces landed
     size_t qcap = 0, bcap = 0, ncap = 0, ocap = 0;
@@ -1240,9 +1243,12 @@ int queue_search(Library& L, Replica& R, Context& c, const uint8_t* d_raw, const
     P.oflow = &pc->oflow;
     if (small) {
         P.zero_stats = reinterpret_cast<uint32_t*>(sd);
-        // the slots this batch's queries add to (q & (kStatSlots - 1), errors in slot 0); the
-        // others stay zero from the block's allocation
-        P.zero_words = (uint32_t)(std::min<size_t>(B, kStatSlots) * sizeof(DevStats) / sizeof(uint32_t));
+        // the slots this batch's queries add to (q & (kStatSlots - 1), errors in slot 0) and those the
+        // context's last small batch added to (a batch of 3 after one of 14 summed the other 11's
+        // slots into its own statistics); the others stay zero from the block's allocation
+        const uint32_t mine = (uint32_t)std::min<size_t>(B, kStatSlots);
+        P.zero_words = (uint32_t)(std::max(mine, c.sio_slots) * sizeof(DevStats) / sizeof(uint32_t));
+        c.sio_slots = mine;
     }
     P.prec = c.d_prec;
     P.pcnt = c.d_pcnt;

@@ -45,8 +45,8 @@ full kernel falls back to exact counting inside the wave, which no counter shows
 Exact table (wave_insert_slot, the full kernel at cmin 1): on the same path a part's base is 0, so
 a term's relative id is id + 1 and its home slot (rel * 0x9E3779B1) >> 21 can be planted: twelve
 terms homing into the last 4 of 2,048 slots, a chain that wraps. Tier 2's table_insert takes its
-base from k_fast's own part planner, which cuts by the postings of the whole query; it is not
-planted here.
+base from k_fast's own part planner, which cuts by the postings of the whole query; it is planted in
+tests/test_gpu_fast_planted.py (tests/fast_cases.py: base 0 and the base of a second part).
 
 Gram dictionary (gram_at's open addressing, set_gram_dict): wide indexes whose every gram homes
 into the last slots of the table, so the one chain wraps to slot 0; queries mix present grams with

@@ -11,15 +11,19 @@ Each test asserts the path counts of ngsLastStats so a routing change cannot sil
 the tier it is meant to cover. The reference behaviour is nGramSearch.hpp:278-301 (searchLong),
 :310-341 (calcScore) and :397-401 (partial_sort to limit).
 """
+import ctypes as C
+import functools
 import random
 import zlib
 
 import pytest
 
+import fast_cases as fc
 from oracle_py import OracleIndex
 from test_gpu_parity import _corpus, assert_exact
 
 import stringsearchlib_amd as ssl
+from stringsearchlib_amd import _native
 
 pytestmark = pytest.mark.gpu
 
@@ -113,11 +117,34 @@ def test_tier2_by_limit(bench20k, thr, limit):
     assert st["general_queries"] == 0, st
 
 
+def _geometry(gi):
+    out = (C.c_uint64 * 17)()
+    assert _native.lib().ngsIndexDigest(gi.handle, out, 17) == 17
+    return out[2], out[7]  # skip buckets, terms per bucket
+
+
+@functools.lru_cache(maxsize=None)
+def _skewed_classes(words, qs, geometry):
+    """What tier 2's planner makes of each query (fast_cases.plan), from the rows: every word is a long
+    term of its own, numbered in order of first appearance."""
+    terms = [w.decode() for w in dict.fromkeys(words)]
+    assert all(len(t) >= 6 for t in terms)
+    _, sp = fc.planner_buckets(*geometry)
+    assert sp * max(len(t) - 2 for t in terms) <= fc.PART_CAP  # no bucket can pass the cap
+    lists = fc.lists_of(terms)
+    return [fc.plan(lists, q.decode(), *geometry).cls for q in qs]
+
+
 @pytest.mark.parametrize("kind", ["skewed", "rows", "short"])
 @pytest.mark.parametrize("thr,limit", [(0.0, 300), (0.3, 1024), (1.0, 129), (0.3, 100)])
 def test_tier2_other_corpora(kind, thr, limit):
-    """Skewed lists (bucket sub-parts in tier 2's planner), aliases / NULL holes / zero and
-    negative weights, and short terms (tier 2's register Levenshtein over shortLib)."""
+    """Skewed lists (many whole-bucket parts per query in tier 2's planner, asserted below with the planner
+    facts of tests/fast_cases.py), aliases / NULL holes / zero and negative weights, and short terms
+    (tier 2's register Levenshtein over shortLib).
+
+    Not bucket sub-parts: the 64 lists of the 4-letter corpus are dense, so the index has 512 skip
+    buckets, the planner reads 256 of 118 terms, and 118 terms of at most 28 grams stay under the
+    4,096 postings at which a bucket is cut by term id. tests/test_gpu_fast_planted.py plants those."""
     rng = random.Random(zlib.crc32(kind.encode()))
     words, rs, wts = _corpus(kind, random.Random(11))
     gi, oi = ssl.StringIndex(words, rs, wts), OracleIndex(words, rs, wts)
@@ -125,6 +152,9 @@ def test_tier2_other_corpora(kind, thr, limit):
     qs = _short_windows(rng, live, 16) + _long_queries(rng, live, 8, 66, 140)
     if kind == "short":
         qs += [w[:rng.randint(4, 8)] for w in rng.sample([w for w in live if len(w) >= 4], 8)]
+    if kind == "skewed":
+        classes = _skewed_classes(tuple(words), tuple(qs), _geometry(gi))
+        assert "multi" in classes and "over" not in classes, classes
     st = _check(gi, oi, qs, thr, limit, f"{kind}")
     assert st["fast_queries"] + st["general_queries"] == len(qs), st
     if limit > 128:
