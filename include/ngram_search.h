@@ -587,6 +587,108 @@ NGS_API uint32_t linkKeys(uint32_t hFrom, uint32_t hTo, float threshold, uint32_
                           float minSimilarity, uint32_t mode, uint32_t batchKeys, uint32_t* match, float* scores,
                           float* sims);
 
+/* ------------------------------------------------------------------------------------
+ * Index sets: several indexes searched as one library, their answers merged on the device (not in
+ * the reference).
+ *
+ * Part. A part p (0 <= p < P <= NGS_SET_MAX_PARTS) is a result block in ngsSearchDevice's layout for
+ * the same n queries: dCounts[n], the records of row i at i * stride (a count above the stride is read
+ * as the stride), a key base keyBase and a key-length table dKeyLen[nKeys]: the characters of each key
+ * as ngsKey / ngsKeyW returns it, without the NUL (ngsKeyLengthsDevice). A record is (p, k, s): part,
+ * local key id, fp32 score.
+ *
+ * Merge order. Records are totally ordered by (1) the order image of the score's fp32 bits
+ * descending (as in "Linking two indexes": numeric order for non-NaN floats with -0 < +0, a NaN
+ * where its bits put it), (2) dKeyLen[k] ascending, 0xFFFFFFFF for k >= nKeys (nothing is read
+ * through such an id), (3) p ascending, (4) k ascending.
+ *
+ * Output. Row i is the first min(L, sum over p of min(dCounts_p[i], stride_p)) records of the union
+ * in that order, L = limit ? limit : 2^31-1, each written as key keyBase_p + k (32-bit arithmetic)
+ * with its score bits unchanged. dCounts[i] is that number; cells past it are unspecified; nothing at
+ * or beyond i * outStride + outStride is written.
+ *
+ * Exactness. A key's score depends on its own row only, a result row is ordered by (score
+ * descending, key id ascending) and key ids are ranks by (length ascending, first appearance
+ * ascending). So for a library cut into contiguous row ranges with no master key in two ranges,
+ * indexed one part per range in order, the merge of the parts' answers at (threshold, limit) is bit
+ * for bit the answer of one index over all rows, with global key id = keyBase_p + k and keyBase_p
+ * the sum of ngsNumKeys of the earlier parts.
+ *
+ * Precondition. Within a part every row is already in merge order, as ngsSearchDevice writes it. For
+ * a row that is not, the order of the output is unspecified; dCounts[i] is still the number above,
+ * every access stays in bounds and every written record is one of the inputs.
+ *
+ * Duplicate keys. Parts are not interned against each other: a master key present in two parts gives
+ * two records under two global ids.
+ * ------------------------------------------------------------------------------------ */
+#define NGS_SET_MAX_PARTS 16u
+typedef struct {
+    const uint32_t* dCounts; const uint32_t* dKeys; const float* dScores;
+    uint32_t stride, keyBase;
+    const uint32_t* dKeyLen; uint32_t nKeys;
+} ngs_merge_part;
+
+/* dLen[i] = the length of key firstKey + i in characters, from the replica on the current device.
+ * Queued on `stream`; nothing waits. 0 ok (nKeys = 0 included); -3 a range past ngsNumKeys or NULL
+ * dLen with nKeys > 0 (checked before the handle); -1 bad handle, -2 un-built index, -3 no replica
+ * on the current device, -4 HIP error. */
+NGS_API int ngsKeyLengthsDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys, uint32_t* dLen, void* stream);
+
+/* The merge defined above of nParts blocks (`parts` is a host array, read before the call returns)
+ * into the caller's block. It takes no handle: the blocks and length tables may come from anywhere,
+ * for instance from a gather of other GPUs' blocks. One kernel, no atomics, reproducible bit for bit;
+ * queued on `stream`, nothing waits. 0 ok (nQueries = 0 included); -3 NULL parts, nParts 0 or above
+ * NGS_SET_MAX_PARTS, nQueries above 2^31-1, NULL outputs with nQueries > 0, a part with NULL
+ * dCounts, a part with a non-zero stride and NULL dKeys or dScores, a part with nKeys > 0 and NULL
+ * dKeyLen, outStride below min(L, sum of the strides) (the sum in 64 bits); -4 HIP error. */
+NGS_API int ngsMergeResultsDevice(const ngs_merge_part* parts, uint32_t nParts, uint32_t nQueries, uint32_t limit,
+                                  uint32_t outStride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
+                                  void* stream);
+
+/* A set: 1..NGS_SET_MAX_PARTS built handles searched as one library. Set ids are a namespace of
+ * their own (indexN never sees them). All members have one ngsCharSize and one ngsGramSize, every one
+ * has a replica on the first member's first device (the set's device), and the sum of their
+ * ngsNumKeys is at most 2^32 - 1. Global key id = base_p + k, base_p the sum of ngsNumKeys of the
+ * earlier members; ngsSetAdd appends, so global ids are stable under it. The set keeps each member's
+ * key-length table on its device (4 bytes a key, built when the member joins). It does not own its
+ * members and remembers each by an identity a reused handle id does not share: once a member has been
+ * disposed every call on the set answers -1 (the host forms 0 with ngsLastError set) until
+ * ngsSetDispose, even if a new index has taken the member's handle id.
+ * ngsSetCreate: the set id, or 0 with ngsLastError set (a HIP invalid-value code for a failed
+ * condition). ngsSetAdd: 0; -1 unknown set or a disposed member; -3 the set is full or a condition
+ * fails; -4 HIP error. ngsSetDispose disposes the set only, never its members. ngsSetParts: the
+ * number of members, -1 for an unknown set or a disposed member. ngsSetNumKeys: the total number of
+ * keys, 0 likewise. ngsSetLocate: 0 with *handle and *localKey (each may be NULL); -1 likewise; -3
+ * keyId >= ngsSetNumKeys. */
+NGS_API uint32_t ngsSetCreate(const uint32_t* handles, uint32_t n);
+NGS_API int ngsSetAdd(uint32_t set, uint32_t handle);
+NGS_API void ngsSetDispose(uint32_t set);
+NGS_API int ngsSetParts(uint32_t set);
+NGS_API uint32_t ngsSetNumKeys(uint32_t set);
+NGS_API int ngsSetLocate(uint32_t set, uint32_t keyId, uint32_t* handle, uint32_t* localKey);
+
+/* ngsSearchDevice over a set: every member searched at (threshold, limit) on the set's device (which
+ * must be current) into blocks the call owns, of stride min(L, nKeys_p), then merged into the caller's
+ * block; keys are global ids. outStride >= min(L, ngsSetNumKeys). Each member normalises the queries
+ * with its own validChar set: a caller who changes one changes them all. Returns when the results
+ * are complete. 0; -1 unknown set or a disposed member; -3 as ngsSearchDevice, or the current device
+ * is not the set's; -4, -5 as ngsSearchDevice. */
+NGS_API int ngsSetSearchDevice(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                               uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
+                               uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream);
+
+/* The host forms, with caller-allocated arrays like selfJoin: counts[nQueries], and the global key
+ * ids and scores of query i at i * stride (stride >= min(L, ngsSetNumKeys)). They return the total
+ * number of records; on failure 0, the counts zeroed and ngsLastError set. The strings are ngsKey* on
+ * what ngsSetLocate answers. scoreBatchSet takes a narrow set, scoreBatchSetW a wide one (0 on a
+ * narrow set), scoreBatchSetU8 UTF-8 queries on a wide set. */
+NGS_API uint32_t scoreBatchSet(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                               uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
+NGS_API uint32_t scoreBatchSetW(uint32_t set, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
+NGS_API uint32_t scoreBatchSetU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                                 uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);

@@ -36,6 +36,12 @@ class NgsStats(C.Structure):
                 ("arena_blocks", C.c_uint64), ("arena_used", C.c_uint64)]
 
 
+class MergePart(C.Structure):
+    """ngs_merge_part: one part of ngsMergeResultsDevice (device addresses as integers)."""
+    _fields_ = [("dCounts", C.c_void_p), ("dKeys", C.c_void_p), ("dScores", C.c_void_p),
+                ("stride", C.c_uint32), ("keyBase", C.c_uint32), ("dKeyLen", C.c_void_p), ("nKeys", C.c_uint32)]
+
+
 def build(jobs: int = 4) -> None:
     """Compile the HIP library for gfx950 in-tree."""
     subprocess.run(["make", "-s", f"-j{jobs}", "-C", CSRC], check=True)
@@ -156,6 +162,18 @@ EXPORTS = [
     # linking two indexes
     ("ngsMatchDevice", {"ngsMatchDevice": (ci, [vp, vp, vp, u32, u32, u32, vp, u32, vp, u32, vp, vp, u32, vp]),
                         "linkKeys": (u32, [u32, u32, f32, u32, u32, f32, u32, u32, PU, P(f32), P(f32)])}),
+    # index sets
+    ("ngsMergeResultsDevice", {"ngsKeyLengthsDevice": (ci, [u32, u32, u32, vp, vp]),
+                               "ngsMergeResultsDevice": (ci, [P(MergePart), u32, u32, u32, u32, vp, vp, vp, vp]),
+                               "ngsSetCreate": (u32, [PU, u32]),
+                               "ngsSetAdd": (ci, [u32, u32]),
+                               "ngsSetDispose": (None, [u32]),
+                               "ngsSetParts": (ci, [u32]),
+                               "ngsSetNumKeys": (u32, [u32]),
+                               "ngsSetLocate": (ci, [u32, u32, PU, PU]),
+                               "ngsSetSearchDevice": _SEARCH_DEVICE,
+                               **_by_width(("", "W", "U8"), {
+                                   "scoreBatchSet": (u32, [u32, STRS, u32, f32, u32, u32, PU, PU, P(f32)])})}),
     ("ngsServeState", {"ngsServeState": (ci, [u32])}),
     ("ngsLastError", {"ngsLastError": (ci, [ci])}),
     ("ngsReplicaDigest", {"ngsReplicaDigest": (ci, [u32, ci, P(u64), ci])}),

@@ -30,6 +30,7 @@
 #include "ngs_join.h"
 #include "ngs_kernels.h"
 #include "ngs_match.h"
+#include "ngs_set.h"
 #include "ngs_sim.h"
 #include "ngs_token.h"
 #include "ngs_utf8.h"
@@ -593,6 +594,7 @@ struct Library {
     // they are done, so no batch kernel queues behind it on a shared hardware queue
     std::atomic<int> batches{0};
     HostIndex host;
+    uint64_t serial = 0;                         // this index's own number, never given twice (index sets)
     int device = 0;                              // first replica's device (or the build device)
     std::vector<std::unique_ptr<Replica>> reps;  // empty until the index is on a GPU
     std::mutex valid_mu;
@@ -660,6 +662,7 @@ struct Library {
 
 std::shared_mutex g_lock;                                        // dllmain.cpp:22
 std::unordered_map<uint32_t, std::unique_ptr<Library>> g_libs;   // dllmain.cpp:24
+uint64_t g_next_serial = 1;                                       // Library::serial (under the exclusive lock)
 thread_local std::vector<int> t_devices;                          // ngsSetDevice(s): this thread's next builds
 
 Library* find_lib(uint32_t h) {
@@ -2373,6 +2376,7 @@ uint32_t new_library(Build&& build) {
     while (g_libs.count(handle) && handle < maxVal) ++handle;
     if (handle == maxVal) return 0;
     auto L = std::make_unique<Library>();
+    L->serial = g_next_serial++;
     set_valid(*L, kDefaultValid, (int)std::strlen(kDefaultValid));
     std::vector<int> devs = t_devices;
     if (devs.empty()) {
@@ -2957,6 +2961,223 @@ uint32_t link_host(uint32_t h_from, uint32_t h_to, float thr, uint32_t limit, ui
     if (scores) std::copy(h_os.begin(), h_os.end(), scores);
     if (sims) std::copy(h_ov.begin(), h_ov.end(), sims);
     return matched;
+}
+
+// ---- index sets (ngsSet* / scoreBatchSet*) ----
+
+// A set names its members and owns their key-length tables on its device; the members stay their
+// own (Library::serial tells a member from a later index under the same handle id).
+struct KeySet {
+    struct Member {
+        uint32_t handle = 0;
+        uint64_t serial = 0;
+        uint32_t base = 0, n_keys = 0;
+        uint32_t* d_len = nullptr;  // [n_keys] on `device`
+    };
+    std::vector<Member> parts;
+    int device = 0;
+    uint32_t csize = 0, gsz = 0;
+    uint64_t n_keys = 0;
+    ~KeySet() {
+        for (Member& m : parts)
+            if (m.d_len) (void)hipFree(m.d_len);
+    }
+};
+std::unordered_map<uint32_t, std::unique_ptr<KeySet>> g_sets;  // a namespace of its own (under g_lock)
+
+// The set and its members' libraries (the caller holds the lock): -1 for an unknown set or a member
+// that has been disposed, whoever holds its handle id now.
+int entry_set(uint32_t set, KeySet*& S, Library** libs) {
+    auto it = g_sets.find(set);
+    if (it == g_sets.end()) return -1;
+    S = it->second.get();
+    for (size_t p = 0; p < S->parts.size(); ++p) {
+        Library* L = find_lib(S->parts[p].handle);
+        if (!L || L->serial != S->parts[p].serial) return -1;
+        libs[p] = L;
+    }
+    return 0;
+}
+
+// `handle` appended to S under the exclusive lock: 0, -3 a condition fails, -4 HIP error. The
+// member's key lengths are computed on the set's device before this returns.
+int set_join(KeySet& S, uint32_t handle) {
+    Library* L = find_lib(handle);
+    if (S.parts.size() >= kSetMaxParts || !L || !L->host.indexed || L->reps.empty()) return -3;
+    const bool first = S.parts.empty();
+    const int device = first ? L->reps.front()->device : S.device;
+    Replica* R = L->replica_at(device);
+    if (!R || (!first && (L->host.csize != S.csize || L->host.gsz != S.gsz)) ||
+        S.n_keys + L->host.n_keys > 0xFFFFFFFFull)
+        return -3;
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    KeySet::Member m;
+    m.handle = handle;
+    m.serial = L->serial;
+    m.base = (uint32_t)S.n_keys;
+    m.n_keys = L->host.n_keys;
+    const bool ok = HIP_CHECK(hipSetDevice(device)) && dev_alloc(&m.d_len, m.n_keys) &&
+                    HIP_CHECK(launch_key_len(R->dev.key_off, 0, m.n_keys, m.d_len, nullptr)) &&
+                    HIP_CHECK(hipStreamSynchronize(nullptr));
+    if (cur >= 0) (void)hipSetDevice(cur);
+    if (!ok) {
+        if (m.d_len) (void)hipFree(m.d_len);
+        return -4;
+    }
+    if (first) {
+        S.device = device;
+        S.csize = L->host.csize;
+        S.gsz = L->host.gsz;
+    }
+    S.n_keys += m.n_keys;
+    S.parts.push_back(m);
+    return 0;
+}
+
+uint32_t set_effective_limit(const KeySet& S, uint32_t limit) {
+    return (uint32_t)std::min<uint64_t>(set_limit(limit), S.n_keys);
+}
+
+// The members' blocks of a set search of up to `rows` queries at `limit`, in M: member p's has the
+// stride min(L, nKeys_p).
+struct SetBlocks {
+    MergeParts parts{};
+    uint64_t records = 0;  // per query, all members
+};
+bool set_blocks(CallScratch& M, const KeySet& S, Library* const* libs, size_t rows, uint32_t limit, SetBlocks& K) {
+    for (size_t p = 0; p < S.parts.size(); ++p) {
+        MergePart& B = K.parts.p[p];
+        B.stride = effective_limit(*libs[p], limit);
+        B.base = S.parts[p].base;
+        B.n_keys = S.parts[p].n_keys;
+        B.len = S.parts[p].d_len;
+        uint32_t *d_n = nullptr, *d_k = nullptr;
+        float* d_s = nullptr;
+        if (!M.alloc(&d_n, rows) || !M.alloc(&d_k, rows * B.stride) || !M.alloc(&d_s, rows * B.stride)) return false;
+        B.counts = d_n;
+        B.keys = d_k;
+        B.scores = d_s;
+        K.records += B.stride;
+    }
+    return true;
+}
+
+// Every member's BatchGuard, held from before the first member's search until the merge has run: no
+// member's server kernel is relaunched in between, so neither a later member's kernels nor the merge
+// queue behind one on a shared hardware queue.
+struct SetGuards {
+    std::unique_ptr<BatchGuard> g[kSetMaxParts];
+    SetGuards(const KeySet& S, Library* const* libs) {
+        for (size_t p = 0; p < S.parts.size(); ++p) g[p] = std::make_unique<BatchGuard>(libs[p]);
+    }
+};
+
+// ngsSetSearchDevice's work (the shared lock and the members' SetGuards held, the set's device
+// current): every member searched into its block, one after another, then the merge queued on s.
+// Nothing waits for the merge.
+int set_search(const KeySet& S, Library* const* libs, const SetBlocks& K, const uint8_t* d_raw, const uint64_t* d_off,
+               uint32_t n, float thr, uint32_t limit, uint32_t out_stride, uint32_t* d_n, uint32_t* d_k, float* d_s,
+               hipStream_t s) {
+    for (size_t p = 0; p < S.parts.size(); ++p) {
+        Replica* R = libs[p]->replica_at(S.device);
+        if (!R) return -3;
+        const MergePart& B = K.parts.p[p];
+        if (const int rc = search_on_replica(*libs[p], *R, d_raw, d_off, n, thr, B.stride, B.stride,
+                                             const_cast<uint32_t*>(B.counts), const_cast<uint32_t*>(B.keys),
+                                             const_cast<float*>(B.scores), s))
+            return rc;
+    }
+    return HIP_CHECK(launch_merge_parts(K.parts, (uint32_t)S.parts.size(), n, limit, out_stride, d_n, d_k, d_s, s)) ? 0 : -4;
+}
+
+// scoreBatchSet / scoreBatchSetW / scoreBatchSetU8: the queries packed and uploaded a chunk at a time
+// (u8: as UTF-8, decoded on the device like a large scoreBatchU8 batch), the set search, the merged
+// block read back into the caller's arrays.
+template <typename CharT>
+uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float thr, uint32_t limit, uint32_t stride,
+                   uint32_t* counts, uint32_t* key_ids, float* scores, bool u8) {
+    if (counts) std::fill(counts, counts + nq, 0u);
+    auto fail = [&](int err) -> uint32_t {  // (counts may hold finished chunks by then)
+        if (err && !t_last_error) t_last_error = err;
+        if (counts) std::fill(counts, counts + nq, 0u);
+        return 0;
+    };
+    if (!counts || (nq && !queries)) return fail((int)hipErrorInvalidValue);
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (entry_set(set, S, libs) != 0) return fail((int)hipErrorInvalidValue);
+    const uint32_t cs = u8 ? (uint32_t)sizeof(uint32_t) : (uint32_t)sizeof(CharT);
+    const uint32_t Lm = set_effective_limit(*S, limit);
+    if (S->csize != cs || stride < Lm || (nq && Lm && (!key_ids || !scores))) return fail((int)hipErrorInvalidValue);
+    if (nq == 0 || Lm == 0) return 0;
+    if (!HIP_CHECK(hipSetDevice(S->device))) return fail(0);
+    SetGuards guards(*S, libs);
+    uint64_t per_query = 0;
+    for (size_t p = 0; p < S->parts.size(); ++p) per_query += effective_limit(*libs[p], limit);
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1, kSimChunkRecords / per_query));
+    // every query's bytes as they go up (u8: the UTF-8 bytes), and the bytes of the largest chunk
+    const uint32_t up = u8 ? 1u : cs;  // bytes per unit of what is uploaded
+    std::vector<size_t> q_len(nq);
+    size_t raw_cap = 0;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        size_t bytes = 0;
+        for (uint32_t i = q0; i < q0 + std::min(chunk, nq - q0); ++i) {
+            q_len[i] = queries[i] ? str_len(queries[i]) : 0;
+            bytes += q_len[i] * up;
+        }
+        raw_cap = std::max(raw_cap, bytes);
+    }
+    CallScratch M;
+    SetBlocks K;
+    uint8_t *d_u8 = nullptr, *d_u8temp = nullptr;
+    uint64_t* d_u8off = nullptr;
+    const size_t u8temp = u8 ? utf8_temp_bytes(chunk) : 0;
+    if (!M.begin(chunk, Lm, u8 ? 4 * raw_cap : raw_cap) || !set_blocks(M, *S, libs, chunk, limit, K) ||
+        (u8 && (!M.alloc(&d_u8, raw_cap + 16) || !M.alloc(&d_u8off, (size_t)chunk + 1) || !M.alloc(&d_u8temp, u8temp))))
+        return fail(0);
+    std::vector<uint32_t> h_n(chunk), h_k((size_t)chunk * Lm);
+    std::vector<float> h_s((size_t)chunk * Lm);
+    std::vector<uint64_t> h_off((size_t)chunk + 1);
+    std::vector<uint8_t> h_raw;
+    uint64_t total = 0;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const uint32_t B = std::min(chunk, nq - q0);
+        h_raw.clear();
+        h_off[0] = 0;
+        for (uint32_t i = 0; i < B; ++i) {
+            const uint8_t* p = reinterpret_cast<const uint8_t*>(queries[q0 + i]);
+            if (q_len[q0 + i]) h_raw.insert(h_raw.end(), p, p + q_len[q0 + i] * up);
+            h_off[i + 1] = h_raw.size();
+        }
+        uint8_t* d_in = u8 ? d_u8 : M.d_raw;
+        uint64_t* d_in_off = u8 ? d_u8off : M.d_off;
+        if (!HIP_CHECK(hipMemcpyAsync(d_in_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice,
+                                      M.stream)) ||
+            (!h_raw.empty() &&
+             !HIP_CHECK(hipMemcpyAsync(d_in, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, M.stream))) ||
+            (u8 && !HIP_CHECK(launch_utf8_decode(d_u8, d_u8off, B, reinterpret_cast<uint32_t*>(M.d_raw), raw_cap,
+                                                 M.d_off, d_u8temp, u8temp, M.stream))))
+            return fail(0);
+        if (set_search(*S, libs, K, M.d_raw, M.d_off, B, thr, limit, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0)
+            return fail(kErrInternal);
+        const size_t rb = (size_t)B * Lm;
+        if (!HIP_CHECK(hipMemcpyAsync(h_n.data(), M.d_n, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_k.data(), M.d_k, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_s.data(), M.d_s, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            !HIP_CHECK(hipStreamSynchronize(M.stream)))
+            return fail(0);
+        for (uint32_t i = 0; i < B; ++i) {
+            const uint32_t c = std::min(h_n[i], Lm);
+            std::copy_n(h_k.begin() + (size_t)i * Lm, c, key_ids + (size_t)(q0 + i) * stride);
+            std::copy_n(h_s.begin() + (size_t)i * Lm, c, scores + (size_t)(q0 + i) * stride);
+            counts[q0 + i] = c;
+            total += c;
+        }
+    }
+    if (total > 0xFFFFFFFFull) return fail((int)hipErrorInvalidValue);  // (the return value is 32-bit)
+    return (uint32_t)total;
 }
 
 // A scan's scratch: one grow-only buffer per (device, stream), 64 KiB at first, so that calls on
@@ -3610,6 +3831,140 @@ NGS_API uint32_t linkKeys(uint32_t hFrom, uint32_t hTo, float threshold, uint32_
                           float minSimilarity, uint32_t mode, uint32_t batchKeys, uint32_t* match, float* scores,
                           float* sims) {
     return link_host(hFrom, hTo, threshold, limit, metric, minSimilarity, mode, batchKeys, match, scores, sims);
+}
+
+NGS_API int ngsKeyLengthsDevice(uint32_t handle, uint32_t firstKey, uint32_t nKeys, uint32_t* dLen, void* stream) {
+    if (nKeys && !dLen) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = nullptr;
+    Replica* R = nullptr;
+    if (const int rc = entry_library(handle, L)) return rc;
+    if (!join_range_ok(*L, firstKey, nKeys)) return -3;
+    if (const int rc = entry_replica(*L, R)) return rc;
+    BatchGuard bg(L);
+    return HIP_CHECK(launch_key_len(R->dev.key_off, firstKey, nKeys, dLen, (hipStream_t)stream)) ? 0 : -4;
+}
+
+NGS_API int ngsMergeResultsDevice(const ngs_merge_part* parts, uint32_t nParts, uint32_t nQueries, uint32_t limit,
+                                  uint32_t outStride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
+                                  void* stream) {
+    if (!parts || nParts == 0 || nParts > kSetMaxParts || nQueries > kInt32Max ||
+        (nQueries && (!dCounts || !dKeys || !dScores)))
+        return -3;
+    MergeParts M{};
+    for (uint32_t p = 0; p < nParts; ++p) {
+        const ngs_merge_part& a = parts[p];
+        if (!a.dCounts || (a.stride && (!a.dKeys || !a.dScores)) || (a.nKeys && !a.dKeyLen)) return -3;
+        M.p[p] = MergePart{a.dCounts, a.dKeys, a.dScores, a.dKeyLen, a.stride, a.keyBase, a.nKeys, 0u};
+    }
+    if (outStride < merge_min_stride(M.p, nParts, limit)) return -3;
+    return HIP_CHECK(launch_merge_parts(M, nParts, nQueries, limit, outStride, dCounts, dKeys, dScores,
+                                        (hipStream_t)stream))
+               ? 0
+               : -4;
+}
+
+NGS_API uint32_t ngsSetCreate(const uint32_t* handles, uint32_t n) {
+    if (!handles || n == 0 || n > kSetMaxParts) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    std::unique_lock<std::shared_mutex> lk(g_lock);
+    auto S = std::make_unique<KeySet>();
+    for (uint32_t p = 0; p < n; ++p)
+        if (const int rc = set_join(*S, handles[p])) {
+            if (rc == -3 || !t_last_error) t_last_error = (int)hipErrorInvalidValue;
+            return 0;
+        }
+    uint32_t id = 1;
+    while (g_sets.count(id) && id < std::numeric_limits<uint32_t>::max()) ++id;
+    if (id == std::numeric_limits<uint32_t>::max()) return 0;
+    g_sets.emplace(id, std::move(S));
+    return id;
+}
+
+NGS_API int ngsSetAdd(uint32_t set, uint32_t handle) {
+    std::unique_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    return set_join(*S, handle);
+}
+
+NGS_API void ngsSetDispose(uint32_t set) {
+    std::unique_lock<std::shared_mutex> lk(g_lock);
+    g_sets.erase(set);
+}
+
+NGS_API int ngsSetParts(uint32_t set) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    return (int)S->parts.size();
+}
+
+NGS_API uint32_t ngsSetNumKeys(uint32_t set) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    return entry_set(set, S, libs) ? 0u : (uint32_t)S->n_keys;
+}
+
+NGS_API int ngsSetLocate(uint32_t set, uint32_t keyId, uint32_t* handle, uint32_t* localKey) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (keyId >= S->n_keys) return -3;
+    size_t p = S->parts.size() - 1;  // the last member whose base is at or below the id (a member may be empty)
+    while (S->parts[p].base > keyId) --p;
+    if (handle) *handle = S->parts[p].handle;
+    if (localKey) *localKey = keyId - S->parts[p].base;
+    return 0;
+}
+
+NGS_API int ngsSetSearchDevice(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                               uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
+                               uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    const uint32_t Lm = set_effective_limit(*S, limit);
+    if (!search_args_ok(dQueryOffsets, nQueries, Lm, outStride, dCounts, dKeys, dScores)) return -3;
+    int cur = -1;
+    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
+    if (cur != S->device) return -3;
+    hipStream_t s = (hipStream_t)stream;
+    if (Lm == 0 || nQueries == 0)
+        return HIP_CHECK(hipMemsetAsync(dCounts, 0, sizeof(uint32_t) * nQueries, s)) && HIP_CHECK(hipStreamSynchronize(s))
+                   ? 0
+                   : -4;
+    // the call's own scratch: the members' blocks, released once the merge has read them
+    CallScratch M;
+    SetBlocks K;
+    if (!set_blocks(M, *S, libs, nQueries, limit, K)) return -4;
+    SetGuards guards(*S, libs);  // (until the final synchronise)
+    if (const int rc = set_search(*S, libs, K, dQueryBytes, dQueryOffsets, nQueries, threshold, limit, outStride, dCounts,
+                                  dKeys, dScores, s))
+        return rc;
+    return HIP_CHECK(hipStreamSynchronize(s)) ? 0 : -4;
+}
+
+NGS_API uint32_t scoreBatchSet(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                               uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores) {
+    return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, false);
+}
+
+NGS_API uint32_t scoreBatchSetW(uint32_t set, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores) {
+    return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, false);
+}
+
+NGS_API uint32_t scoreBatchSetU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                                 uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores) {
+    return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, true);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

@@ -1,0 +1,132 @@
+// ngs_set.h — index sets: the result blocks of several indexes for the same queries
+// merged into the block one index over all their rows would have given. The definitions shared by
+// the host reference routine and the device kernels (ngs_set.hip).
+//
+// A part p (0 <= p < P <= kSetMaxParts) is a result block in ngsSearchDevice's layout for the same n
+// queries: counts_p[n], the records of row i at i * stride_p (a count above the stride is read as the
+// stride), a key base base_p and a key-length table len_p[nKeys_p] (characters of the key as ngsKey /
+// ngsKeyW returns it, without the NUL). A record is (p, k, s): part, local key id, fp32 score.
+//
+// Merge order. Records are totally ordered by
+//   1. sim_order_bits(bits(s)) descending (ngs_sim.h: numeric order for non-NaN floats with -0 < +0,
+//      a NaN where its bits put it),
+//   2. len_p[k] ascending, 0xFFFFFFFF for k >= nKeys_p (nothing is read through such an id),
+//   3. p ascending,
+//   4. k ascending.
+// Row i of the output is the first min(L, sum_p min(counts_p[i], stride_p)) records of the union in
+// that order, L = limit ? limit : 2^31-1, each written as key base_p + k (u32 arithmetic) with its
+// score bits unchanged; counts[i] is that number, cells past it are unspecified and nothing at or
+// beyond i * out_stride + out_stride is written.
+//
+// Why this is the whole library's answer: a key's score depends on its own row only, a result row is
+// (score descending, key id ascending), and key ids are ranks by (length ascending, first appearance
+// ascending). For a library cut into contiguous row ranges with no master key in two of them the
+// whole library's order is therefore (score desc, length asc, part asc, local id asc), and the top L
+// of the union lies in the union of the parts' top L.
+//
+// Duplicate keys. Parts are not interned against each other: a master key that is present in two
+// parts gives two records, under two global ids.
+//
+// Precondition the kernel uses: within a part a row is already in merge order (ngsSearchDevice's rows
+// are: score descending, then k ascending, and k ascends with the length). For a row that is not,
+// the order of the output is unspecified; counts[i] is still the number above, every access stays in
+// bounds and every written record is one of the inputs.
+//
+// Plain C++17 without a HIP include: g++ compiles the host routine alone (tests/sanitize).
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "ngs_sim.h"
+
+namespace ngs {
+
+constexpr uint32_t kSetMaxParts = 16;            // NGS_SET_MAX_PARTS
+constexpr uint32_t kSetNoLen = 0xFFFFFFFFu;      // the length of a key id past its part's table
+constexpr uint32_t kSetLimitAll = 0x7FFFFFFFu;   // limit 0
+// k_merge_parts' cut-overs (the tests sit on them):
+//  - a launch whose rows hold at most kSetOneWaveRecords records each (sum_p min(stride_p, L)) runs
+//    one wave per query, any other a workgroup of kSetThreads;
+//  - a query whose rows hold at most kSetLdsRecords records (sum_p min(counts_p[i], stride_p, L))
+//    stages their comparators in LDS (8 bytes each: 64,000 bytes, which with the row's bookkeeping
+//    stays within the 64 KiB a launch gets without asking for more), any other reads them from HBM.
+constexpr uint32_t kSetOneWaveRecords = 256;
+constexpr uint32_t kSetThreads = 256;
+constexpr uint32_t kSetLdsRecords = 8000;
+
+// One part as the kernel takes it, by value: 16 of them are the 768 bytes of MergeParts.
+struct MergePart {
+    const uint32_t* counts;
+    const uint32_t* keys;
+    const float* scores;
+    const uint32_t* len;
+    uint32_t stride, base, n_keys, pad;
+};
+static_assert(sizeof(MergePart) == 48, "16 parts x 48 bytes travel in the kernel arguments");
+struct MergeParts {
+    MergePart p[kSetMaxParts];
+};
+
+// The comparator of a record: smaller = earlier. Ties are settled by (p, k).
+NGS_HD inline uint64_t set_cmp(uint32_t score_bits, uint32_t len) {
+    return ((uint64_t)(~sim_order_bits(score_bits)) << 32) | len;
+}
+NGS_HD inline uint32_t set_limit(uint32_t limit) { return limit ? limit : kSetLimitAll; }
+
+// ---- host reference routine (the kernel restates it as a merge by ranks) ----
+// Row i of the merge of P parts into out_keys / out_scores at i * out_stride: a plain stable sort of
+// the union. Returns the row's count. The caller's out_stride is at least min(L, sum_p stride_p).
+inline uint32_t merge_row(const MergePart* parts, uint32_t P, uint32_t i, uint32_t limit, uint32_t out_stride,
+                          uint32_t* out_keys, float* out_scores) {
+    struct Rec {
+        uint64_t cmp;
+        uint32_t p, k, bits;
+    };
+    std::vector<Rec> recs;
+    for (uint32_t p = 0; p < P; ++p) {
+        const MergePart& M = parts[p];
+        const uint32_t c = M.counts[i] < M.stride ? M.counts[i] : M.stride;
+        for (uint32_t r = 0; r < c; ++r) {
+            const uint32_t k = M.keys[(size_t)i * M.stride + r];
+            uint32_t bits;
+            std::memcpy(&bits, M.scores + (size_t)i * M.stride + r, sizeof bits);
+            recs.push_back({set_cmp(bits, k < M.n_keys ? M.len[k] : kSetNoLen), p, k, bits});
+        }
+    }
+    std::stable_sort(recs.begin(), recs.end(), [](const Rec& a, const Rec& b) {
+        if (a.cmp != b.cmp) return a.cmp < b.cmp;
+        if (a.p != b.p) return a.p < b.p;
+        return a.k < b.k;
+    });
+    const uint64_t L = set_limit(limit);
+    const uint32_t n = (uint32_t)(recs.size() < L ? recs.size() : L);
+    for (uint32_t r = 0; r < n; ++r) {
+        out_keys[(size_t)i * out_stride + r] = parts[recs[r].p].base + recs[r].k;
+        std::memcpy(out_scores + (size_t)i * out_stride + r, &recs[r].bits, sizeof(float));
+    }
+    return n;
+}
+inline void merge_rows(const MergePart* parts, uint32_t P, uint32_t n, uint32_t limit, uint32_t out_stride,
+                       uint32_t* out_counts, uint32_t* out_keys, float* out_scores) {
+    for (uint32_t i = 0; i < n; ++i) out_counts[i] = merge_row(parts, P, i, limit, out_stride, out_keys, out_scores);
+}
+// the least out_stride a merge may be given: min(L, sum_p stride_p), the sum in 64 bits
+inline uint64_t merge_min_stride(const MergePart* parts, uint32_t P, uint32_t limit) {
+    uint64_t sum = 0;
+    for (uint32_t p = 0; p < P; ++p) sum += parts[p].stride;
+    return std::min<uint64_t>(sum, set_limit(limit));
+}
+
+#if defined(__HIPCC__)
+// Both queue on s and wait for nothing.
+// len[i] = characters of key first + i (key_off counts characters, one NUL per key)
+hipError_t launch_key_len(const uint64_t* key_off, uint32_t first, uint32_t n, uint32_t* len, hipStream_t s);
+hipError_t launch_merge_parts(const MergeParts& parts, uint32_t P, uint32_t n, uint32_t limit, uint32_t out_stride,
+                              uint32_t* out_counts, uint32_t* out_keys, float* out_scores, hipStream_t s);
+#endif
+
+}  // namespace ngs

@@ -345,6 +345,11 @@ class StringIndex:
         _native.lib().ngsLastStats(self.handle, C.byref(st))
         return {f: getattr(st, f) for f, _ in st._fields_}
 
+    def key_lengths_device(self, first: int, count: int, d_len: int, stream: int = 0) -> None:
+        """ngsKeyLengthsDevice: d_len[i] = the characters of key first + i, queued on `stream`."""
+        _ok(_native.lib().ngsKeyLengthsDevice(self.handle, first, count, d_len or None, stream or None),
+            "ngsKeyLengthsDevice")
+
     def search_device(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int, out_stride: int,
                       d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> None:
         """ngsSearchDevice on raw device pointers (e.g. torch tensors' data_ptr())."""
@@ -647,3 +652,116 @@ class Utf8StringIndex(WideStringIndex):
         """ngsSearchDeviceU8: search_device with UTF-8 query bytes and offsets."""
         _ok(_native.lib().ngsSearchDeviceU8(self.handle, d_bytes, d_offsets, n, threshold, limit, out_stride,
                                             d_counts, d_keys, d_scores, stream or None), "ngsSearchDeviceU8")
+
+
+# ---- index sets: several indexes searched as one library (include/ngram_search.h) --------
+def merge_results_device(parts, n: int, limit: int, out_stride: int, d_counts: int, d_keys: int, d_scores: int,
+                         stream: int = 0) -> None:
+    """ngsMergeResultsDevice on raw device pointers. parts: up to 16 of (d_counts, d_keys, d_scores, stride,
+    key_base, d_key_len, n_keys), each a result block of ngsSearchDevice's layout for the same n queries
+    with its keys' lengths (key_lengths_device); the output block is what one index over all the parts'
+    rows would have answered, with key ids key_base + k. Queued on `stream`; nothing waits."""
+    arr = (_native.MergePart * max(1, len(parts)))()
+    for a, (pc, pk, ps, stride, base, plen, nk) in zip(arr, parts):
+        a.dCounts, a.dKeys, a.dScores, a.dKeyLen = pc or None, pk or None, ps or None, plen or None
+        a.stride, a.keyBase, a.nKeys = stride, base, nk
+    _ok(_native.lib().ngsMergeResultsDevice(arr, len(parts), n, limit, out_stride, d_counts, d_keys, d_scores,
+                                            stream or None), "ngsMergeResultsDevice")
+
+
+class IndexSet:
+    """Indexes of one class and gram size searched as one library (ngsSet*): partitions of a library, or a
+    base and the parts appended to it. Global key id = the keys of the earlier parts + the local id; the
+    answers are those of one index over all the parts' rows when no master key is in two parts. The set
+    holds its members (none is collected under it) but does not own them: dispose() leaves them alive."""
+
+    def __init__(self, parts):
+        parts = list(parts)
+        if not parts:
+            raise ValueError("an IndexSet needs at least one index")
+        L = _native.lib()
+        hs = (C.c_uint32 * len(parts))(*[p.handle for p in parts])
+        L.ngsLastError(1)
+        self.set_id = L.ngsSetCreate(hs, len(parts))
+        if not self.set_id:
+            raise RuntimeError(f"ngsSetCreate failed: error {L.ngsLastError(1)} (1..16 built indexes of one "
+                               f"character and gram size on one device)")
+        self._parts = parts
+
+    @property
+    def parts(self):
+        return list(self._parts)
+
+    def add(self, index) -> None:
+        """ngsSetAdd: `index` becomes the last part; the ids of the keys already there stay."""
+        _ok(_native.lib().ngsSetAdd(self.set_id, index.handle), "ngsSetAdd")
+        self._parts.append(index)
+
+    def append(self, words, row_size: int = 1, weights=None):
+        """Builds an index of the first part's class and gram size over `words` and adds it; returns it."""
+        first = self._parts[0]
+        index = type(first)(words, row_size, weights, gram_size=first.gram_size())
+        try:
+            self.add(index)
+        except Exception:
+            index.dispose()
+            raise
+        return index
+
+    def num_keys(self) -> int:
+        return _native.lib().ngsSetNumKeys(self.set_id)
+
+    def locate(self, key_id: int):
+        """(member index, local key id) of a global key id."""
+        h, k = C.c_uint32(), C.c_uint32()
+        if _native.lib().ngsSetLocate(self.set_id, key_id, C.byref(h), C.byref(k)):
+            raise IndexError(key_id)
+        return next(p for p in self._parts if p.handle == h.value), k.value
+
+    def key(self, key_id: int):
+        index, k = self.locate(key_id)
+        return index.key(k)
+
+    def score_batch(self, queries, threshold: float = 0.0, limit: int = 100):
+        """scoreBatchSet / W / U8 by the members' class: one list of (key, score) per query."""
+        L, first = _native.lib(), self._parts[0]
+        what = "scoreBatchSet" + first._fn["scoreBatch"][len("scoreBatch"):]
+        fn = getattr(L, what)
+        nq = len(queries)
+        qs = first._queries(queries)
+        stride = max(1, min(limit if limit else INT32_MAX, self.num_keys()))
+        counts = (C.c_uint32 * max(1, nq))()
+        keys = (C.c_uint32 * max(1, nq * stride))()
+        scores = (C.c_float * max(1, nq * stride))()
+        L.ngsLastError(1)
+        total = fn(self.set_id, qs, nq, threshold, limit, stride, counts, keys, scores)
+        if not total:
+            _check(what)
+        strings = {}
+
+        def name(g):
+            if g not in strings:
+                strings[g] = self.key(g)
+            return strings[g]
+
+        out = [[(name(keys[i * stride + j]), scores[i * stride + j]) for j in range(counts[i])] for i in range(nq)]
+        assert sum(map(len, out)) == total
+        return out
+
+    def search_device(self, d_bytes: int, d_offsets: int, n: int, threshold: float, limit: int, out_stride: int,
+                      d_counts: int, d_keys: int, d_scores: int, stream: int = 0) -> None:
+        """ngsSetSearchDevice on raw device pointers: search_device over the set, keys as global ids."""
+        _ok(_native.lib().ngsSetSearchDevice(self.set_id, d_bytes, d_offsets, n, threshold, limit, out_stride,
+                                             d_counts, d_keys, d_scores, stream or None), "ngsSetSearchDevice")
+
+    def dispose(self) -> None:
+        """Disposes the set; the members stay."""
+        if self.set_id:
+            _native.lib().ngsSetDispose(self.set_id)
+            self.set_id = 0
+
+    def __del__(self):
+        try:
+            self.dispose()
+        except Exception:
+            pass
