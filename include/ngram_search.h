@@ -689,6 +689,67 @@ NGS_API uint32_t scoreBatchSetW(uint32_t set, const wchar_t* const* queries, uin
 NGS_API uint32_t scoreBatchSetU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
                                  uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
 
+/* ---- The later stages over a set ----
+ * Key ids are the set's global ones everywhere below. Member p owns g iff base_p <= g < base_p +
+ * nKeys_p. Every answer is the one a single index over all the members' rows would give (no master
+ * key in two members), except that a matched term id is local to the member ngsSetLocate gives for
+ * the record's key (ngsTerm on that handle).
+ *
+ * ngsSetSimilarityDeviceM: ngsSimilarityDeviceM over a set. The similarity of record (i, g) is
+ * ngsSimilarityDeviceM's for local key g - base_p on member p, metric, wildcard rule, the 4,096
+ * character cap, "a count above the stride reads as the stride" and the fp32 formula included; dTerms
+ * (may be NULL) receives the member's local term id, the smallest among equal fp32 values. A g >=
+ * ngsSetNumKeys gives -1.0f and 0xFFFFFFFF, nothing read through it. The query is normalised once per
+ * query with the validChar set of the set's first member: a caller who changes one member's set
+ * changes them all. One kernel launch for the whole block, queued on `stream`; the first call (and the
+ * first NGS_SIM_TOKEN_SORT call) builds what a member lacks, as ngsSimilarityDeviceM does, and nothing
+ * waits after that. With NGS_SIM_TOKEN_SORT the queries are taken as given (ngsTokenSortDevice on the
+ * first member first). -3 NULL arguments as ngsSimilarityDeviceM or an unknown metric (before the set
+ * is looked at); -1 unknown set or a disposed member; -3 the current device is not the set's; -4 HIP
+ * error. ngsSetRerankDeviceM: that, then ngsRerankDeviceM's filter and order in place; -3 also for
+ * stride > 4,096 or a NaN minSimilarity. */
+NGS_API int ngsSetSimilarityDeviceM(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                    uint32_t nQueries, uint32_t stride, const uint32_t* dCounts, const uint32_t* dKeys,
+                                    uint32_t metric, float* dSim, uint32_t* dTerms, void* stream);
+NGS_API int ngsSetRerankDeviceM(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
+                                float* dSim, uint32_t* dTerms, uint32_t metric, float minSimilarity, void* stream);
+
+/* ngsKeyQueryBytes / ngsKeyQueriesDevice for the global key range [firstKey, firstKey + nKeys), which
+ * may span members: the same layout (offsets ascend from 0; on a wide set dBytes is 4-byte aligned),
+ * the same return codes with -1 for an unknown set or a disposed member and -3 when the current device
+ * is not the set's; nKeys = 0 is valid. ngsSetKeyQueryBytes answers 0 for a bad set or range. */
+NGS_API uint64_t ngsSetKeyQueryBytes(uint32_t set, uint32_t firstKey, uint32_t nKeys);
+NGS_API int ngsSetKeyQueriesDevice(uint32_t set, uint32_t firstKey, uint32_t nKeys, uint8_t* dBytes, uint64_t capBytes,
+                                   uint64_t* dOffsets, void* stream);
+
+/* ngsSelfJoinDevice over a set: the gather above, ngsSetSearchDevice's search at limit + 1, then
+ * ngsDropSelfDevice with the global firstKey. outStride >= min((limit ? limit : 2^31-1) + 1,
+ * ngsSetNumKeys), else -3. Returns when the results are complete; codes as ngsSelfJoinDevice and
+ * ngsSetSearchDevice. */
+NGS_API int ngsSetSelfJoinDevice(uint32_t set, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                                 uint32_t outStride, uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream);
+
+/* scoreBatchSimM* over a set, with caller-allocated arrays like scoreBatchSet: sims and terms (may be
+ * NULL; the members' local term ids) in keyIds' layout. The calls token-sort their own copy of the
+ * queries with NGS_SIM_TOKEN_SORT. min(limit ? limit : 2^31-1, ngsSetNumKeys) above 4,096 fails with
+ * NGS_ERR_RERANK_LIMIT. selfJoinSet: selfJoin over global ids. dedupKeysSet: dedupKeysM over global ids,
+ * labels[ngsSetNumKeys]; batches may cross members; returns the number of clusters. Failure as in the
+ * single-index forms: 0, the counts zeroed, ngsLastError set. */
+NGS_API uint32_t scoreBatchSetSimM(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                                   uint32_t limit, uint32_t metric, float minSimilarity, uint32_t stride,
+                                   uint32_t* counts, uint32_t* keyIds, float* scores, float* sims, uint32_t* terms);
+NGS_API uint32_t scoreBatchSetSimMW(uint32_t set, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                    uint32_t limit, uint32_t metric, float minSimilarity, uint32_t stride,
+                                    uint32_t* counts, uint32_t* keyIds, float* scores, float* sims, uint32_t* terms);
+NGS_API uint32_t scoreBatchSetSimMU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                                     uint32_t limit, uint32_t metric, float minSimilarity, uint32_t stride,
+                                     uint32_t* counts, uint32_t* keyIds, float* scores, float* sims, uint32_t* terms);
+NGS_API uint32_t selfJoinSet(uint32_t set, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                             uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
+NGS_API uint32_t dedupKeysSet(uint32_t set, float threshold, uint32_t limit, uint32_t metric, float minSimilarity,
+                              uint32_t batchKeys, uint32_t* labels);
+
 /* The server of `handle`: 0 none, 1 set up but its kernel not running, 2 its kernel running; -1
  * bad handle (tests). */
 NGS_API int ngsServeState(uint32_t handle);

@@ -174,6 +174,17 @@ EXPORTS = [
                                "ngsSetSearchDevice": _SEARCH_DEVICE,
                                **_by_width(("", "W", "U8"), {
                                    "scoreBatchSet": (u32, [u32, STRS, u32, f32, u32, u32, PU, PU, P(f32)])})}),
+    # the later stages over a set
+    ("ngsSetSimilarityDeviceM", {
+        "ngsSetSimilarityDeviceM": (ci, [u32, vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]),
+        "ngsSetRerankDeviceM": (ci, [u32, vp, vp, u32, u32, vp, vp, vp, vp, vp, u32, f32, vp]),
+        "ngsSetKeyQueryBytes": (u64, [u32, u32, u32]),
+        "ngsSetKeyQueriesDevice": (ci, [u32, u32, u32, vp, u64, vp, vp]),
+        "ngsSetSelfJoinDevice": (ci, [u32, u32, u32, f32, u32, u32, vp, vp, vp, vp]),
+        **_by_width(("", "W", "U8"), {
+            "scoreBatchSetSimM": (u32, [u32, STRS, u32, f32, u32, u32, f32, u32, PU, PU, P(f32), P(f32), PU])}),
+        "selfJoinSet": (u32, [u32, u32, u32, f32, u32, u32, PU, PU, P(f32)]),
+        "dedupKeysSet": (u32, [u32, f32, u32, u32, f32, u32, PU])}),
     ("ngsServeState", {"ngsServeState": (ci, [u32])}),
     ("ngsLastError", {"ngsLastError": (ci, [ci])}),
     ("ngsReplicaDigest", {"ngsReplicaDigest": (ci, [u32, ci, P(u64), ci])}),

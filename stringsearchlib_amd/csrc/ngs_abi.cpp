@@ -2751,24 +2751,34 @@ uint32_t join_batch_keys(uint32_t want, uint32_t nk, uint32_t Ls) {
     return (uint32_t)std::min<size_t>({want ? want : kJoinBatchKeys, std::max(nk, 1u), fit});
 }
 
-uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr, uint32_t limit, uint32_t stride,
-                        uint32_t* counts, uint32_t* key_ids, float* scores) {
-    if (counts) std::fill(counts, counts + nk, 0u);
-    std::shared_lock<std::shared_mutex> lk(g_lock);
-    Library* L = find_lib(handle);
-    auto fail = [&](int err) -> uint32_t {  // (counts may hold finished batches by then)
-        if (err && !t_last_error) t_last_error = err;
-        if (counts) std::fill(counts, counts + nk, 0u);
-        return 0;
-    };
-    if (!L || !L->host.indexed || !counts || !join_range_ok(*L, first, nk)) return fail((int)hipErrorInvalidValue);
-    const uint32_t Lm = effective_limit(*L, limit);
-    if (stride < Lm || (nk && Lm && (!key_ids || !scores))) return fail((int)hipErrorInvalidValue);
-    if (nk == 0 || Lm == 0) return 0;
-    BatchGuard bg(L);
-    Replica& R = *L->reps.front();
-    if (!HIP_CHECK(hipSetDevice(R.device))) return fail(0);
-    const uint32_t Ls = join_search_limit(*L, limit);
+// What a host join runs over: one index on its first replica (OneJoin), or an index set (SetJoin,
+// further down). Key ids are the source's own: an index's, or a set's global ones. The caller holds
+// the lock and the guards, and the source's device is current.
+struct OneJoin {
+    Library& L;
+    Replica& R;
+    uint32_t n_keys() const { return L.host.n_keys; }
+    uint32_t search_limit(uint32_t limit) const { return join_search_limit(L, limit); }
+    uint64_t max_query_bytes(uint32_t first, uint32_t nk, uint32_t B) const {
+        return join_max_query_bytes(L, first, nk, B);
+    }
+    bool blocks(CallScratch&, size_t, uint32_t) { return true; }  // (a set's members' blocks)
+    // one batch into M's arrays, queued on M.stream
+    int batch(CallScratch& M, uint32_t first, uint32_t n, float thr, uint32_t limit, uint32_t stride) {
+        return join_batch(L, R, first, n, thr, limit, stride, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream, false);
+    }
+    // the batch's similarities into d_v (the gathered queries token-sorted in place when flagged)
+    int similarity(CallScratch& M, uint32_t n, uint32_t stride, float* d_v, uint32_t metric) {
+        return queue_similarity(L, R, M.d_raw, M.d_off, n, stride, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric, false,
+                                0.0f, M.stream, M.d_raw);
+    }
+};
+
+// selfJoin / selfJoinSet behind their fronts: keys [first, first + nk) of J a batch at a time.
+template <class J, class Fail>
+uint32_t self_join_run(J& j, uint32_t first, uint32_t nk, float thr, uint32_t limit, uint32_t stride, uint32_t* counts,
+                       uint32_t* key_ids, float* scores, Fail&& fail) {
+    const uint32_t Ls = j.search_limit(limit);
     const uint32_t B = join_batch_keys(0, nk, Ls);
     // a batch's records come back packed ({key id, score bits} in row order behind the rows' offsets,
     // as ngsPackResults writes them): the bytes read back follow the records, not keys x stride
@@ -2776,16 +2786,14 @@ uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr,
     uint8_t* d_tmp = nullptr;
     uint32_t *d_pos = nullptr, *d_rec = nullptr;
     const size_t tmp_bytes = std::max<size_t>(pack_pairs_temp_bytes(B), 1 << 16);
-    if (!M.begin(B, Ls, join_max_query_bytes(*L, first, nk, B)) || !M.alloc(&d_pos, (size_t)B + 1) ||
+    if (!M.begin(B, Ls, j.max_query_bytes(first, nk, B)) || !j.blocks(M, B, limit) || !M.alloc(&d_pos, (size_t)B + 1) ||
         !M.alloc(&d_rec, 2 * (size_t)B * Ls) || !M.alloc(&d_tmp, tmp_bytes))
         return fail(0);
     std::vector<uint32_t> h_pos((size_t)B + 1), h_rec;
     uint64_t total = 0;
     for (uint32_t done = 0; done < nk; done += B) {
         const uint32_t n = std::min(B, nk - done);
-        if (join_batch(*L, R, first + done, n, thr, limit, Ls, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream,
-                       false) != 0)
-            return fail(kErrInternal);
+        if (j.batch(M, first + done, n, thr, limit, Ls) != 0) return fail(kErrInternal);
         if (!HIP_CHECK(launch_pack_pairs(M.d_n, M.d_k, M.d_s, n, Ls, d_pos, d_rec, d_tmp, tmp_bytes, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_pos.data(), d_pos, sizeof(uint32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost,
                                       M.stream)) ||
@@ -2814,41 +2822,58 @@ uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr,
     return (uint32_t)total;
 }
 
-uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric, float min_sim, uint32_t batch_keys,
-                    uint32_t* labels) {
-    if (!labels || limit == 0 || limit > kRerankMaxStride || min_sim != min_sim || !sim_metric_ok(metric)) {
-        t_last_error = labels && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
-        return 0;
-    }
+uint32_t self_join_host(uint32_t handle, uint32_t first, uint32_t nk, float thr, uint32_t limit, uint32_t stride,
+                        uint32_t* counts, uint32_t* key_ids, float* scores) {
+    if (counts) std::fill(counts, counts + nk, 0u);
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = find_lib(handle);
-    if (!L || !L->host.indexed) {
-        t_last_error = (int)hipErrorInvalidValue;
+    auto fail = [&](int err) -> uint32_t {  // (counts may hold finished batches by then)
+        if (err && !t_last_error) t_last_error = err;
+        if (counts) std::fill(counts, counts + nk, 0u);
         return 0;
-    }
-    const uint32_t nk = L->host.n_keys;
-    if (nk == 0) return 0;
+    };
+    if (!L || !L->host.indexed || !counts || !join_range_ok(*L, first, nk)) return fail((int)hipErrorInvalidValue);
+    const uint32_t Lm = effective_limit(*L, limit);
+    if (stride < Lm || (nk && Lm && (!key_ids || !scores))) return fail((int)hipErrorInvalidValue);
+    if (nk == 0 || Lm == 0) return 0;
     BatchGuard bg(L);
     Replica& R = *L->reps.front();
-    if (!HIP_CHECK(hipSetDevice(R.device))) return 0;
-    const uint32_t Ls = join_search_limit(*L, limit);
+    if (!HIP_CHECK(hipSetDevice(R.device))) return fail(0);
+    OneJoin j{*L, R};
+    return self_join_run(j, first, nk, thr, limit, stride, counts, key_ids, scores, fail);
+}
+
+// the checks dedupKeys* and dedupKeysSet make before any handle is looked at
+bool dedup_args_ok(uint32_t limit, uint32_t metric, float min_sim, const uint32_t* labels) {
+    if (labels && limit != 0 && limit <= kRerankMaxStride && min_sim == min_sim && sim_metric_ok(metric)) return true;
+    t_last_error = labels && limit > kRerankMaxStride ? kErrRerankLimit : (int)hipErrorInvalidValue;
+    return false;
+}
+
+// dedupKeys* / dedupKeysSet behind their fronts: every key of J joined a batch at a time, the batches'
+// records merged into one label array on the device.
+template <class J>
+uint32_t dedup_run(J& j, float thr, uint32_t limit, uint32_t metric, float min_sim, uint32_t batch_keys,
+                   uint32_t* labels) {
+    const uint32_t nk = j.n_keys();
+    if (nk == 0) return 0;
+    const uint32_t Ls = j.search_limit(limit);
     const uint32_t B = join_batch_keys(batch_keys, nk, Ls);
     const bool verify = min_sim > -1.0f;  // every similarity is >= -1: nothing to filter at or below it
     CallScratch M;
     uint32_t* d_lab = nullptr;
     float* d_v = nullptr;
-    if (!M.begin(B, Ls, join_max_query_bytes(*L, 0, nk, B)) || !M.alloc(&d_lab, nk) ||
+    if (!M.begin(B, Ls, j.max_query_bytes(0, nk, B)) || !j.blocks(M, B, limit) || !M.alloc(&d_lab, nk) ||
         (verify && !M.alloc(&d_v, (size_t)B * Ls)))
         return 0;
     // the label array stays on the device across the batches: finished and read back once
     for (uint32_t done = 0; done < nk; done += B) {
         const uint32_t n = std::min(B, nk - done);
-        if (join_batch(*L, R, done, n, thr, limit, Ls, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream, false) != 0) {
+        if (j.batch(M, done, n, thr, limit, Ls) != 0) {
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (verify && (queue_similarity(*L, R, M.d_raw, M.d_off, n, Ls, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric,
-                                        false, 0.0f, M.stream, M.d_raw) != 0 ||
+        if (verify && (j.similarity(M, n, Ls, d_v, metric) != 0 ||
                        !HIP_CHECK(launch_keep_similar(M.d_n, M.d_k, M.d_s, d_v, n, Ls, min_sim, M.stream))))
             return 0;
         const uint32_t flags = (done == 0 ? kClusterInit : 0u) | (done + n == nk ? kClusterFinish : 0u);
@@ -2860,6 +2885,23 @@ uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric,
     uint32_t clusters = 0;
     for (uint32_t k = 0; k < nk; ++k) clusters += labels[k] == k;
     return clusters;
+}
+
+uint32_t dedup_host(uint32_t handle, float thr, uint32_t limit, uint32_t metric, float min_sim, uint32_t batch_keys,
+                    uint32_t* labels) {
+    if (!dedup_args_ok(limit, metric, min_sim, labels)) return 0;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    Library* L = find_lib(handle);
+    if (!L || !L->host.indexed) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    if (L->host.n_keys == 0) return 0;
+    BatchGuard bg(L);
+    Replica& R = *L->reps.front();
+    if (!HIP_CHECK(hipSetDevice(R.device))) return 0;
+    OneJoin j{*L, R};
+    return dedup_run(j, thr, limit, metric, min_sim, batch_keys, labels);
 }
 
 // ---- linking two indexes (linkKeys) ----
@@ -3091,12 +3133,150 @@ int set_search(const KeySet& S, Library* const* libs, const SetBlocks& K, const 
     return HIP_CHECK(launch_merge_parts(K.parts, (uint32_t)S.parts.size(), n, limit, out_stride, d_n, d_k, d_s, s)) ? 0 : -4;
 }
 
+// ---- the later stages over a set (ngsSetSimilarityDeviceM .. dedupKeysSet) ----
+
+// The current device is the set's: -4 no device, -3 another one (the caller's buffers and stream
+// belong to the current one).
+int set_device_current(const KeySet& S) {
+    int cur = -1;
+    if (!HIP_CHECK(hipGetDevice(&cur))) return -4;
+    return cur == S.device ? 0 : -3;
+}
+
+// queue_similarity over a set: every member's key_term map (and with kSimTokenSort its sorted terms)
+// built where missing, as the single-index path builds them, then one launch of k_sim_set for the
+// whole block, under the first member's validChar set. The set's device is current.
+int queue_set_similarity(const KeySet& S, Library* const* libs, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n,
+                         uint32_t stride, uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, uint32_t* d_t,
+                         uint32_t metric, bool rerank, float min_sim, hipStream_t s, uint8_t* d_sort = nullptr) {
+    if (n == 0) return 0;
+    SimMembers T{};
+    for (size_t p = 0; p < S.parts.size(); ++p) {
+        Replica* R = libs[p]->replica_at(S.device);
+        if (!R) return -3;
+        bool ok = true;
+        const uint32_t* key_term = sim_key_term(*R, ok);
+        if (!ok) return -4;
+        DevIndex X = R->dev;
+        if ((metric & kSimTokenSort) && !sim_sorted_terms(*R, X)) return -4;
+        T.m[p] = SimMember{X.kt_off, X.kt_term, key_term, X.term_off, X.term_bytes, X.n_keys, X.n_terms,
+                           S.parts[p].base, 0u};
+    }
+    uint32_t valid[8];
+    {
+        std::lock_guard<std::mutex> g(libs[0]->valid_mu);
+        std::memcpy(valid, libs[0]->valid, sizeof valid);
+    }
+    if ((metric & kSimTokenSort) && d_sort && !HIP_CHECK(launch_token_sort(valid, S.csize, d_raw, d_off, n, d_sort, s)))
+        return -4;
+    if (!HIP_CHECK(launch_similarity_set(T, (uint32_t)S.parts.size(), S.csize, valid, d_raw, d_off, n, stride, d_n, d_k,
+                                         sim_metric_base(metric), d_v, d_t, s)))
+        return -4;
+    if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
+    return 0;
+}
+
+// f(p, local first key, keys, position in the range) for every member holding keys of the global
+// range [first, first + n), in order
+template <class F>
+void set_segments(const KeySet& S, uint32_t first, uint32_t n, F&& f) {
+    const uint64_t end = (uint64_t)first + n;
+    for (size_t p = 0; p < S.parts.size(); ++p) {
+        const uint64_t base = S.parts[p].base;
+        const uint64_t a = std::max<uint64_t>(first, base), b = std::min<uint64_t>(end, base + S.parts[p].n_keys);
+        if (a < b) f(p, (uint32_t)(a - base), (uint32_t)(b - a), (uint32_t)(a - first));
+    }
+}
+bool set_range_ok(const KeySet& S, uint32_t first, uint32_t n) { return (uint64_t)first + n <= S.n_keys; }
+uint64_t set_query_bytes(const KeySet& S, Library* const* libs, uint32_t first, uint32_t n) {
+    uint64_t bytes = 0;
+    set_segments(S, first, n, [&](size_t p, uint32_t k0, uint32_t nk, uint32_t) {
+        bytes += join_query_bytes(*libs[p], k0, nk);
+    });
+    return bytes;
+}
+uint64_t set_max_query_bytes(const KeySet& S, Library* const* libs, uint32_t first, uint32_t nk, uint32_t B) {
+    uint64_t most = 0;
+    for (uint32_t k0 = first; k0 < first + nk; k0 += B)
+        most = std::max(most, set_query_bytes(S, libs, k0, std::min(B, first + nk - k0)));
+    return most;
+}
+// join_search_limit over the set's keys
+uint32_t set_join_limit(const KeySet& S, uint32_t limit) {
+    return (uint32_t)std::min<uint64_t>((uint64_t)(limit ? limit : kInt32Max) + 1u, S.n_keys);
+}
+
+// The keys of the global range as one query batch in ngsKeyQueriesDevice's layout: each member's
+// keys gathered behind the earlier members' bytes, its offsets (written from 0) moved up by them.
+// A member's first offset is its predecessor's last; the stream orders the two writes.
+bool set_key_queries(const KeySet& S, Library* const* libs, uint32_t first, uint32_t n, uint8_t* d_raw,
+                     uint64_t* d_off, hipStream_t s) {
+    if (n == 0) return HIP_CHECK(hipMemsetAsync(d_off, 0, sizeof(uint64_t), s));
+    uint64_t at = 0;
+    bool ok = true;
+    set_segments(S, first, n, [&](size_t p, uint32_t k0, uint32_t nk, uint32_t i0) {
+        Replica* R = libs[p]->replica_at(S.device);
+        if (!ok || !R) {
+            ok = false;
+            return;
+        }
+        const uint64_t bytes = join_query_bytes(*libs[p], k0, nk);
+        ok = HIP_CHECK(launch_key_queries(R->dev, k0, nk, bytes, d_raw + at, d_off + i0, s)) &&
+             HIP_CHECK(launch_shift_offsets(d_off + i0, (uint64_t)nk + 1u, at, s));
+        at += bytes;
+    });
+    return ok;
+}
+
+// join_batch over a set (its device current, the lock and the members' guards held): the gather, the
+// set search with one record more, the key's own record dropped by its global id.
+int set_join_batch(const KeySet& S, Library* const* libs, const SetBlocks& K, uint32_t first, uint32_t n, float thr,
+                   uint32_t limit, uint32_t stride, uint8_t* d_raw, uint64_t* d_off, uint32_t* d_n, uint32_t* d_k,
+                   float* d_s, hipStream_t s, bool wait) {
+    if (!set_key_queries(S, libs, first, n, d_raw, d_off, s)) return -4;
+    if (const int rc = set_search(S, libs, K, d_raw, d_off, n, thr, set_join_limit(S, limit), stride, d_n, d_k, d_s, s))
+        return rc;
+    if (!HIP_CHECK(launch_drop_self(d_n, d_k, d_s, n, stride, first, limit, s))) return -4;
+    return !wait || HIP_CHECK(hipStreamSynchronize(s)) ? 0 : -4;
+}
+
+// OneJoin's counterpart: key ids are the set's global ones, a batch may span members.
+struct SetJoin {
+    const KeySet& S;
+    Library* const* libs;
+    SetBlocks K{};
+    uint32_t n_keys() const { return (uint32_t)S.n_keys; }
+    uint32_t search_limit(uint32_t limit) const { return set_join_limit(S, limit); }
+    uint64_t max_query_bytes(uint32_t first, uint32_t nk, uint32_t B) const {
+        return set_max_query_bytes(S, libs, first, nk, B);
+    }
+    bool blocks(CallScratch& M, size_t rows, uint32_t limit) { return set_blocks(M, S, libs, rows, search_limit(limit), K); }
+    int batch(CallScratch& M, uint32_t first, uint32_t n, float thr, uint32_t limit, uint32_t stride) {
+        return set_join_batch(S, libs, K, first, n, thr, limit, stride, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream,
+                              false);
+    }
+    int similarity(CallScratch& M, uint32_t n, uint32_t stride, float* d_v, uint32_t metric) {
+        return queue_set_similarity(S, libs, M.d_raw, M.d_off, n, stride, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric, false,
+                                    0.0f, M.stream, M.d_raw);
+    }
+};
+
+// scoreBatchSetSimM*'s part of set_batch: the re-rank by `metric` behind the set search, the
+// similarities and (terms != null) the members' matched term ids read back in the records' layout
+struct SetSim {
+    uint32_t metric;
+    float min_sim;
+    float* sims;
+    uint32_t* terms;
+};
+
 // scoreBatchSet / scoreBatchSetW / scoreBatchSetU8: the queries packed and uploaded a chunk at a time
 // (u8: as UTF-8, decoded on the device like a large scoreBatchU8 batch), the set search, the merged
-// block read back into the caller's arrays.
+// block read back into the caller's arrays. With `sim` (scoreBatchSetSimM*) the similarity and the
+// re-rank run between the two, on the call's own copy of the queries.
 template <typename CharT>
 uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float thr, uint32_t limit, uint32_t stride,
-                   uint32_t* counts, uint32_t* key_ids, float* scores, bool u8) {
+                   uint32_t* counts, uint32_t* key_ids, float* scores, bool u8, const SetSim* sim = nullptr) {
     if (counts) std::fill(counts, counts + nq, 0u);
     auto fail = [&](int err) -> uint32_t {  // (counts may hold finished chunks by then)
         if (err && !t_last_error) t_last_error = err;
@@ -3104,13 +3284,16 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
         return 0;
     };
     if (!counts || (nq && !queries)) return fail((int)hipErrorInvalidValue);
+    if (sim && (sim->min_sim != sim->min_sim || !sim_metric_ok(sim->metric))) return fail((int)hipErrorInvalidValue);
     std::shared_lock<std::shared_mutex> lk(g_lock);
     KeySet* S = nullptr;
     Library* libs[kSetMaxParts] = {};
     if (entry_set(set, S, libs) != 0) return fail((int)hipErrorInvalidValue);
     const uint32_t cs = u8 ? (uint32_t)sizeof(uint32_t) : (uint32_t)sizeof(CharT);
     const uint32_t Lm = set_effective_limit(*S, limit);
-    if (S->csize != cs || stride < Lm || (nq && Lm && (!key_ids || !scores))) return fail((int)hipErrorInvalidValue);
+    if (S->csize != cs || stride < Lm || (nq && Lm && (!key_ids || !scores || (sim && !sim->sims))))
+        return fail((int)hipErrorInvalidValue);
+    if (sim && Lm > kRerankMaxStride) return fail(kErrRerankLimit);
     if (nq == 0 || Lm == 0) return 0;
     if (!HIP_CHECK(hipSetDevice(S->device))) return fail(0);
     SetGuards guards(*S, libs);
@@ -3134,11 +3317,15 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
     uint8_t *d_u8 = nullptr, *d_u8temp = nullptr;
     uint64_t* d_u8off = nullptr;
     const size_t u8temp = u8 ? utf8_temp_bytes(chunk) : 0;
+    const size_t recs = (size_t)chunk * Lm;
+    float* d_v = nullptr;
+    uint32_t* d_t = nullptr;
     if (!M.begin(chunk, Lm, u8 ? 4 * raw_cap : raw_cap) || !set_blocks(M, *S, libs, chunk, limit, K) ||
-        (u8 && (!M.alloc(&d_u8, raw_cap + 16) || !M.alloc(&d_u8off, (size_t)chunk + 1) || !M.alloc(&d_u8temp, u8temp))))
+        (u8 && (!M.alloc(&d_u8, raw_cap + 16) || !M.alloc(&d_u8off, (size_t)chunk + 1) || !M.alloc(&d_u8temp, u8temp))) ||
+        (sim && (!M.alloc(&d_v, recs) || (sim->terms && !M.alloc(&d_t, recs)))))
         return fail(0);
-    std::vector<uint32_t> h_n(chunk), h_k((size_t)chunk * Lm);
-    std::vector<float> h_s((size_t)chunk * Lm);
+    std::vector<uint32_t> h_n(chunk), h_k(recs), h_t(d_t ? recs : 0);
+    std::vector<float> h_s(recs), h_v(sim ? recs : 0);
     std::vector<uint64_t> h_off((size_t)chunk + 1);
     std::vector<uint8_t> h_raw;
     uint64_t total = 0;
@@ -3162,16 +3349,23 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
             return fail(0);
         if (set_search(*S, libs, K, M.d_raw, M.d_off, B, thr, limit, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0)
             return fail(kErrInternal);
+        if (sim && queue_set_similarity(*S, libs, M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, sim->metric, true,
+                                        sim->min_sim, M.stream, M.d_raw) != 0)
+            return fail(kErrInternal);
         const size_t rb = (size_t)B * Lm;
         if (!HIP_CHECK(hipMemcpyAsync(h_n.data(), M.d_n, sizeof(uint32_t) * B, hipMemcpyDeviceToHost, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_k.data(), M.d_k, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream)) ||
             !HIP_CHECK(hipMemcpyAsync(h_s.data(), M.d_s, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream)) ||
+            (sim && !HIP_CHECK(hipMemcpyAsync(h_v.data(), d_v, sizeof(float) * rb, hipMemcpyDeviceToHost, M.stream))) ||
+            (d_t && !HIP_CHECK(hipMemcpyAsync(h_t.data(), d_t, sizeof(uint32_t) * rb, hipMemcpyDeviceToHost, M.stream))) ||
             !HIP_CHECK(hipStreamSynchronize(M.stream)))
             return fail(0);
         for (uint32_t i = 0; i < B; ++i) {
             const uint32_t c = std::min(h_n[i], Lm);
             std::copy_n(h_k.begin() + (size_t)i * Lm, c, key_ids + (size_t)(q0 + i) * stride);
             std::copy_n(h_s.begin() + (size_t)i * Lm, c, scores + (size_t)(q0 + i) * stride);
+            if (sim) std::copy_n(h_v.begin() + (size_t)i * Lm, c, sim->sims + (size_t)(q0 + i) * stride);
+            if (d_t) std::copy_n(h_t.begin() + (size_t)i * Lm, c, sim->terms + (size_t)(q0 + i) * stride);
             counts[q0 + i] = c;
             total += c;
         }
@@ -3965,6 +4159,142 @@ NGS_API uint32_t scoreBatchSetW(uint32_t set, const wchar_t* const* queries, uin
 NGS_API uint32_t scoreBatchSetU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
                                  uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores) {
     return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, true);
+}
+
+NGS_API int ngsSetSimilarityDeviceM(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                    uint32_t nQueries, uint32_t stride, const uint32_t* dCounts, const uint32_t* dKeys,
+                                    uint32_t metric, float* dSim, uint32_t* dTerms, void* stream) {
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || !sim_metric_ok(metric)) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (const int rc = set_device_current(*S)) return rc;
+    SetGuards guards(*S, libs);
+    return queue_set_similarity(*S, libs, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
+                                const_cast<uint32_t*>(dKeys), nullptr, dSim, dTerms, metric, false, 0.0f,
+                                (hipStream_t)stream);
+}
+
+NGS_API int ngsSetRerankDeviceM(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
+                                uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
+                                float* dSim, uint32_t* dTerms, uint32_t metric, float minSimilarity, void* stream) {
+    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
+        stride > kRerankMaxStride || minSimilarity != minSimilarity || !sim_metric_ok(metric))
+        return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (const int rc = set_device_current(*S)) return rc;
+    SetGuards guards(*S, libs);
+    return queue_set_similarity(*S, libs, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim,
+                                dTerms, metric, true, minSimilarity, (hipStream_t)stream);
+}
+
+NGS_API uint64_t ngsSetKeyQueryBytes(uint32_t set, uint32_t firstKey, uint32_t nKeys) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (entry_set(set, S, libs) != 0 || !set_range_ok(*S, firstKey, nKeys)) return 0;
+    return set_query_bytes(*S, libs, firstKey, nKeys);
+}
+
+NGS_API int ngsSetKeyQueriesDevice(uint32_t set, uint32_t firstKey, uint32_t nKeys, uint8_t* dBytes, uint64_t capBytes,
+                                   uint64_t* dOffsets, void* stream) {
+    if (!dOffsets || (capBytes && !dBytes)) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (!set_range_ok(*S, firstKey, nKeys)) return -3;
+    const uint64_t total = set_query_bytes(*S, libs, firstKey, nKeys);
+    if (capBytes < total || (S->csize == 4 && (reinterpret_cast<uintptr_t>(dBytes) & 3u))) return -3;
+    if (const int rc = set_device_current(*S)) return rc;
+    SetGuards guards(*S, libs);
+    return set_key_queries(*S, libs, firstKey, nKeys, dBytes, dOffsets, (hipStream_t)stream) ? 0 : -4;
+}
+
+NGS_API int ngsSetSelfJoinDevice(uint32_t set, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                                 uint32_t outStride, uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream) {
+    if (!dCounts || (nKeys && (!dKeys || !dScores))) return -3;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    const uint32_t Ls = set_join_limit(*S, limit);
+    if (!set_range_ok(*S, firstKey, nKeys) || outStride < Ls) return -3;
+    if (const int rc = set_device_current(*S)) return rc;
+    if (nKeys == 0) return 0;
+    SetGuards guards(*S, libs);  // (until the final synchronise)
+    // the call's own scratch: the gathered queries and the members' blocks, released once the merge
+    // has read them (the results and the stream are the caller's)
+    CallScratch M;
+    SetBlocks K;
+    if (!M.alloc(&M.d_raw, set_query_bytes(*S, libs, firstKey, nKeys) + 16) || !M.alloc(&M.d_off, (size_t)nKeys + 1) ||
+        !set_blocks(M, *S, libs, nKeys, Ls, K))
+        return -4;
+    return set_join_batch(*S, libs, K, firstKey, nKeys, threshold, limit, outStride, M.d_raw, M.d_off, dCounts, dKeys,
+                          dScores, (hipStream_t)stream, true);
+}
+
+NGS_API uint32_t scoreBatchSetSimM(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                                   uint32_t limit, uint32_t metric, float minSimilarity, uint32_t stride,
+                                   uint32_t* counts, uint32_t* keyIds, float* scores, float* sims, uint32_t* terms) {
+    const SetSim sim{metric, minSimilarity, sims, terms};
+    return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, false, &sim);
+}
+
+NGS_API uint32_t scoreBatchSetSimMW(uint32_t set, const wchar_t* const* queries, uint32_t nQueries, float threshold,
+                                    uint32_t limit, uint32_t metric, float minSimilarity, uint32_t stride,
+                                    uint32_t* counts, uint32_t* keyIds, float* scores, float* sims, uint32_t* terms) {
+    const SetSim sim{metric, minSimilarity, sims, terms};
+    return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, false, &sim);
+}
+
+NGS_API uint32_t scoreBatchSetSimMU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
+                                     uint32_t limit, uint32_t metric, float minSimilarity, uint32_t stride,
+                                     uint32_t* counts, uint32_t* keyIds, float* scores, float* sims, uint32_t* terms) {
+    const SetSim sim{metric, minSimilarity, sims, terms};
+    return set_batch(set, queries, nQueries, threshold, limit, stride, counts, keyIds, scores, true, &sim);
+}
+
+NGS_API uint32_t selfJoinSet(uint32_t set, uint32_t firstKey, uint32_t nKeys, float threshold, uint32_t limit,
+                             uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores) {
+    if (counts) std::fill(counts, counts + nKeys, 0u);
+    auto fail = [&](int err) -> uint32_t {  // (counts may hold finished batches by then)
+        if (err && !t_last_error) t_last_error = err;
+        if (counts) std::fill(counts, counts + nKeys, 0u);
+        return 0;
+    };
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (!counts || entry_set(set, S, libs) != 0 || !set_range_ok(*S, firstKey, nKeys))
+        return fail((int)hipErrorInvalidValue);
+    const uint32_t Lm = set_effective_limit(*S, limit);
+    if (stride < Lm || (nKeys && Lm && (!keyIds || !scores))) return fail((int)hipErrorInvalidValue);
+    if (nKeys == 0 || Lm == 0) return 0;
+    if (!HIP_CHECK(hipSetDevice(S->device))) return fail(0);
+    SetGuards guards(*S, libs);
+    SetJoin j{*S, libs};
+    return self_join_run(j, firstKey, nKeys, threshold, limit, stride, counts, keyIds, scores, fail);
+}
+
+NGS_API uint32_t dedupKeysSet(uint32_t set, float threshold, uint32_t limit, uint32_t metric, float minSimilarity,
+                              uint32_t batchKeys, uint32_t* labels) {
+    if (!dedup_args_ok(limit, metric, minSimilarity, labels)) return 0;
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (entry_set(set, S, libs) != 0) {
+        t_last_error = (int)hipErrorInvalidValue;
+        return 0;
+    }
+    if (S->n_keys == 0 || !HIP_CHECK(hipSetDevice(S->device))) return 0;
+    SetGuards guards(*S, libs);
+    SetJoin j{*S, libs};
+    return dedup_run(j, threshold, limit, metric, minSimilarity, batchKeys, labels);
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

@@ -105,6 +105,8 @@ inline void uf_finish(uint32_t* parent, uint32_t n_labels) {
 // off[0..n] and the bytes of keys [first, first + n) as a query batch; total = join_query_off(.., n, ..)
 hipError_t launch_key_queries(const DevIndex& X, uint32_t first, uint32_t n, uint64_t total, uint8_t* bytes,
                               uint64_t* off, hipStream_t s);
+// off[i] += add, i < n: the offsets of a batch gathered behind another one's bytes
+hipError_t launch_shift_offsets(uint64_t* off, uint64_t n, uint64_t add, hipStream_t s);
 hipError_t launch_drop_self(uint32_t* counts, uint32_t* keys, float* scores, uint32_t n, uint32_t stride,
                             uint32_t first, uint32_t limit, hipStream_t s);
 // records with sim < min_sim removed from every row, the others kept in order (keys and scores; with

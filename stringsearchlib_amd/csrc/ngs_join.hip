@@ -3,6 +3,7 @@
 //
 // k_key_queries   the keys [first, first + n) as a query batch: offsets from key_off by formula, the
 //                 bytes as a segmented gather (a thread owns 16 output bytes);
+// k_shift_offsets a batch's offsets moved up by a constant: the keys of several indexes in one batch (§9.8);
 // k_drop_self     one wave per row: the row's own record found by ballot, the later records moved up
 //                 in chunks of 64, the row cut to the limit;
 // k_keep_similar  one wave per row: the records with sim >= min_sim kept in order (dedupKeys);
@@ -95,6 +96,12 @@ __global__ __launch_bounds__(256) void k_key_queries(const uint64_t* __restrict_
         for (uint32_t d = 0; d < 4; ++d)
             if (whole[d]) *reinterpret_cast<uint32_t*>(vbase + v0 + 4u * d) = w[d];
     }
+}
+
+// off[i] += add for i < n: a gather of several indexes' keys into one batch (launch_shift_offsets)
+__global__ __launch_bounds__(256) void k_shift_offsets(uint64_t* __restrict__ off, uint64_t n, uint64_t add) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n) off[i] += add;
 }
 
 // ---- drop-self ----
@@ -259,6 +266,14 @@ hipError_t launch_key_queries(const DevIndex& X, uint32_t first, uint32_t n, uin
     else
         hipLaunchKernelGGL(k_key_queries<false>, dim3((uint32_t)blocks), dim3(256), 0, s, X.key_off, X.key_bytes, first,
                            n, total, bytes, off, mis);
+    return hipGetLastError();
+}
+
+hipError_t launch_shift_offsets(uint64_t* off, uint64_t n, uint64_t add, hipStream_t s) {
+    if (!n || !add) return hipSuccess;
+    const uint64_t blocks = (n + 255u) / 256u;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_shift_offsets, dim3((uint32_t)blocks), dim3(256), 0, s, off, n, add);
     return hipGetLastError();
 }
 

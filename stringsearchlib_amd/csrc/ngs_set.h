@@ -121,7 +121,68 @@ inline uint64_t merge_min_stride(const MergePart* parts, uint32_t P, uint32_t li
     return std::min<uint64_t>(sum, set_limit(limit));
 }
 
+// ---- the similarity over a set ----
+// A record is (query i, global key id g). Member p owns g iff base_p <= g < base_p + nKeys_p; the
+// members tile [0, total) in order (base_0 = 0, base_{p+1} = base_p + nKeys_p; a member may be empty).
+// The record's similarity and matched term are those of ngsSimilarityDeviceM for the local key
+// g - base_p on member p (ngs_sim.h: metric, wildcard rule, kSimMaxQuery, the fp32 formula); the term
+// id is the member's local one. g >= total gives kSimNone and kSimNoTerm, nothing read through it.
+// The query is normalised once, with the validChar set of the set's first member: a caller who
+// changes one member's set changes them all (§9.7).
+//
+// One member as k_sim_set takes it, by value: its key -> terms arrays (kt_off / kt_term, or key_term
+// where every key has one pair: kt_off null) and its terms (term_off / term_bytes, or the
+// token-sorted pair). Members of both storage forms mix in one launch.
+struct SimMember {
+    const uint32_t* kt_off;
+    const uint32_t* kt_term;
+    const uint32_t* key_term;
+    const uint64_t* term_off;
+    const uint8_t* term_bytes;
+    uint32_t n_keys, n_terms, base, pad;
+};
+static_assert(sizeof(SimMember) == 56, "16 members x 56 bytes travel in the kernel arguments");
+struct SimMembers {
+    SimMember m[kSetMaxParts];
+};
+constexpr uint32_t kSetNoPart = 0xFFFFFFFFu;  // no member owns the id
+
+// ---- host reference routines (k_sim_set restates them per lane) ----
+// The member owning g among P members of ascending bases: the last whose base is at or below g
+// (empty members share a base with their successor and own nothing); kSetNoPart for g >= total.
+inline uint32_t sim_set_part(const SimMember* m, uint32_t P, uint32_t g) {
+    if (P == 0 || (uint64_t)g >= (uint64_t)m[P - 1].base + m[P - 1].n_keys) return kSetNoPart;
+    uint32_t p = 0;
+    for (uint32_t i = 1; i < P; ++i) p += m[i].base <= g ? 1u : 0u;
+    return p;
+}
+// The record rule: the member p and the local key of g, and the member's local term ids the record
+// compares, in order, into terms[0 .. returned count) (at most cap are written). A term id at or
+// past n_terms is skipped as the kernel skips it. False, and nothing read through g, for g >= total.
+inline bool sim_set_record(const SimMember* m, uint32_t P, uint32_t g, uint32_t& p, uint32_t& key, uint32_t* terms,
+                           uint32_t cap, uint32_t& n_terms) {
+    n_terms = 0;
+    p = sim_set_part(m, P, g);
+    if (p == kSetNoPart) return false;
+    const SimMember& M = m[p];
+    key = g - M.base;
+    const uint32_t j = M.kt_off ? M.kt_off[key] : 0u, je = M.kt_off ? M.kt_off[key + 1] : 1u;
+    for (uint32_t i = j; i < je; ++i) {
+        const uint32_t t = M.kt_off ? M.kt_term[i] : M.key_term[key];
+        if (t >= M.n_terms) continue;
+        if (n_terms < cap) terms[n_terms] = t;
+        ++n_terms;
+    }
+    return true;
+}
+
 #if defined(__HIPCC__)
+// launch_similarity over the P members of T (character size cs, the first member's validChar set):
+// one launch for the whole block; terms (may be null) receives the members' local term ids.
+hipError_t launch_similarity_set(const SimMembers& T, uint32_t P, uint32_t cs, const uint32_t valid[8],
+                                 const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
+                                 const uint32_t* counts, const uint32_t* keys, uint32_t metric, float* sim,
+                                 uint32_t* terms, hipStream_t s);
 // Both queue on s and wait for nothing.
 // len[i] = characters of key first + i (key_off counts characters, one NUL per key)
 hipError_t launch_key_len(const uint64_t* key_off, uint32_t first, uint32_t n, uint32_t* len, hipStream_t s);

@@ -13,9 +13,11 @@
 // The metric (ngs_sim.h: Levenshtein, OSA, partial) and the matched-term output are template
 // parameters of k_sim, the term array one of k_rerank: launch_similarity and
 // launch_rerank pick the instantiation; the entry points without a metric are kSimLevenshtein, no terms.
+// k_sim_set: k_sim over an index set, the member of every record looked up in the wave.
 #include <hip/hip_runtime.h>
 
 #include "ngs_common.h"
+#include "ngs_set.h"
 #include "ngs_sim.h"
 
 namespace ngs {
@@ -357,6 +359,255 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
     }
 }
 
+// ---- the similarity over an index set ----
+// k_sim with the index looked up per record: a key id is global, the member owning it comes from a
+// count over the members' ascending bases (set_member), and every later step of the chain key ->
+// term -> term_off -> term_bytes goes through that member's descriptor. The descriptors travel by
+// value in the kernel arguments and are copied to LDS once, so that lanes in different members
+// index them without a trip to memory; a lane carries its member's index beside its key. Members
+// with kt_off / kt_term and members with the key_term map mix freely. The matched term is the
+// member's local term id. Everything about the query (wildcard, trim, masks, the systolic words)
+// is k_sim's, as are the recurrences.
+__device__ __forceinline__ uint32_t set_member(const SimMember* m, uint32_t P, uint32_t g) {
+    uint32_t p = 0;  // bases ascend from 0: the last member whose base is at or below g
+    for (uint32_t i = 1; i < P; ++i) p += m[i].base <= g ? 1u : 0u;
+    return p;
+}
+__device__ __forceinline__ void key_terms(const SimMember& M, uint32_t key, uint32_t& j, uint32_t& je) {
+    if (M.kt_off) {
+        j = M.kt_off[key];
+        je = M.kt_off[key + 1];
+    } else {
+        j = 0;
+        je = 1;
+    }
+}
+__device__ __forceinline__ uint32_t term_at(const SimMember& M, uint32_t key, uint32_t j) {
+    return M.kt_off ? M.kt_term[j] : M.key_term[key];
+}
+
+template <bool kWide, uint32_t kMetric, bool kTerms>
+__global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32_t total, SimArgs A) {
+    constexpr uint32_t cs = kWide ? 4u : 1u;
+    __shared__ uint64_t s_mask[256];
+    __shared__ uint32_t s_key[kSimSlots];
+    __shared__ uint32_t s_valid[8];
+    __shared__ SimMember s_m[kSetMaxParts];
+    const uint32_t lane = threadIdx.x, q = blockIdx.x;
+    if (lane < 8) s_valid[lane] = A.V.w[lane];
+    if (lane == 0) {
+#pragma unroll
+        for (uint32_t p = 0; p < kSetMaxParts; ++p)
+            if (p < P) s_m[p] = T.m[p];  // (constant indexes: scalar loads; entries from P on are never read)
+    }
+    __syncthreads();
+
+    const uint32_t count = min(A.counts[q], A.stride);
+    if (count == 0) return;
+    const uint32_t* keys = A.keys + (size_t)q * A.stride;
+    float* out = A.sim + (size_t)q * A.stride;
+    uint32_t* out_t = kTerms ? A.terms + (size_t)q * A.stride : nullptr;
+    const uint64_t qa = A.off[q], qe = A.off[q + 1];
+    const uint64_t n = qe > qa ? (qe - qa) / cs : 0;
+    const uint8_t* rq = A.raw + qa;
+
+    float fixed = 0.0f;
+    bool is_fixed = false;
+    uint64_t first = n, m64 = 0;
+    if (n == 0 || (n == 1 && ld_char(rq, 0, cs) == (uint32_t)'*')) {
+        fixed = kSimWildcard;
+        is_fixed = true;
+    } else {
+        for (uint64_t base = 0; base < n; base += 64) {
+            const uint64_t i = base + lane;
+            const uint64_t bal = __ballot(i < n && sim_keeps(s_valid, ld_char(rq, i, cs), cs));
+            if (bal) {
+                first = base + (uint32_t)__ffsll((unsigned long long)bal) - 1u;
+                break;
+            }
+        }
+        if (first < n) {
+            uint64_t last = first;
+            for (uint64_t base = 0; base < n; base += 64) {
+                const uint64_t i = base + lane;
+                const uint64_t bal = __ballot(i < n && sim_keeps(s_valid, ld_char(rq, n - 1 - i, cs), cs));
+                if (bal) {
+                    last = n - 1 - (base + (uint32_t)__ffsll((unsigned long long)bal) - 1u);
+                    break;
+                }
+            }
+            m64 = last - first + 1;
+        }
+        if (m64 > kSimMaxQuery) {
+            fixed = kSimNone;
+            is_fixed = true;
+        }
+    }
+    if (is_fixed) {
+        for (uint32_t r = lane; r < count; r += 64) {
+            out[r] = fixed;
+            if constexpr (kTerms) out_t[r] = kSimNoTerm;
+        }
+        return;
+    }
+    const uint32_t m = (uint32_t)m64;
+    const uint8_t* nq = rq + first * cs;
+
+    if (m <= 64) {
+        // ---- short path: lanes are records, each in the member of its key ----
+        const uint32_t qc = lane < m ? sim_norm(s_valid, ld_char(nq, lane, cs), cs) : kSimEmpty;
+        uint64_t mine = 0;
+        for (uint32_t i = 0; i < m; ++i) mine |= __shfl(qc, (int)i) == qc ? 1ull << i : 0ull;
+        if (kWide) {
+            s_key[lane] = kSimEmpty;
+            s_key[lane + 64] = kSimEmpty;
+        } else {
+            for (uint32_t i = lane; i < 256; i += 64) s_mask[i] = 0;
+        }
+        __syncthreads();
+        if (lane < m) {
+            if (!kWide) {
+                s_mask[qc] = mine;
+            } else if ((uint32_t)__ffsll((unsigned long long)mine) - 1u == lane) {
+                uint32_t s = sim_slot(qc);
+                for (;;) {
+                    const uint32_t old = atomicCAS(&s_key[s], kSimEmpty, qc);
+                    if (old == kSimEmpty || old == qc) break;
+                    s = (s + 1u) & (kSimSlots - 1u);
+                }
+                s_mask[s] = mine;
+            }
+        }
+        __syncthreads();
+
+        // a record's place in its member: the member p, the local key, the terms [j, je) still to
+        // compare and the first of them, tt = [ta, tb). A global id at or past `total` has none.
+        struct Rec {
+            uint32_t p, key, j, je, tt;
+            uint64_t ta, tb;
+        };
+        auto first_term = [&](uint32_t g) {
+            Rec f{0, 0, 0, 0, kSimNoTerm, 0, 0};
+            if (g >= total) return f;
+            f.p = set_member(s_m, P, g);
+            const SimMember& M = s_m[f.p];
+            f.key = g - M.base;
+            if (f.key >= M.n_keys) return f;
+            key_terms(M, f.key, f.j, f.je);
+            if (f.j >= f.je) return f;
+            const uint32_t t = term_at(M, f.key, f.j);
+            if (t >= M.n_terms) return f;
+            f.tt = t;
+            f.ta = M.term_off[t];
+            f.tb = M.term_off[t + 1];
+            return f;
+        };
+        // rounds of 64 records; the next round's member -> key -> term -> offsets chain is issued
+        // before the current round's recurrence
+        Rec c = first_term(lane < count ? keys[lane] : kSimEmpty);
+        for (uint32_t base = 0; base < count; base += 64) {
+            const uint32_t r = base + lane, rn = r + 64;
+            const Rec nx = first_term(rn < count ? keys[rn] : kSimEmpty);
+            const SimMember& M = s_m[c.p];
+            float best = kSimNone;
+            uint32_t best_t = kSimNoTerm;
+            while (c.j < c.je) {
+                if (c.tb > c.ta) {
+                    const uint32_t L = (uint32_t)(c.tb - c.ta);
+                    uint32_t d = kMetric == kSimPartial ? 0u : L;
+                    if (m) {
+                        if (kWide)
+                            d = myers_wide<kMetric>(s_mask, s_key, m, reinterpret_cast<const uint32_t*>(M.term_bytes) + c.ta, L);
+                        else d = myers_narrow<kMetric>(s_mask, m, M.term_bytes, c.ta, L);
+                    }
+                    sim_take<kTerms>(best, best_t, sim_of<kMetric>(d, m, L), c.tt);
+                }
+                if (++c.j < c.je) {
+                    const uint32_t t = term_at(M, c.key, c.j);
+                    c.ta = c.tb = 0;
+                    if (t < M.n_terms) {
+                        c.tt = t;
+                        c.ta = M.term_off[t];
+                        c.tb = M.term_off[t + 1];
+                    }
+                }
+            }
+            if (r < count) {
+                out[r] = best;
+                if constexpr (kTerms) out_t[r] = best_t;
+            }
+            c = nx;
+        }
+        return;
+    }
+
+    // ---- long path: the systolic pipeline, one record at a time; its member is uniform over the wave ----
+    const uint32_t W = (m + 63u) / 64u;
+    const uint32_t rows = lane + 1u < W ? 64u : (lane < W ? m - 64u * lane : 0u);
+    const uint64_t top = rows ? 1ull << (rows - 1u) : 0ull;
+    const uint64_t rowmask = rows == 64u ? ~0ull : (1ull << rows) - 1ull;
+    constexpr uint32_t kRegs = kWide ? 64u : 16u;
+    uint32_t qw[kRegs];
+#pragma unroll
+    for (uint32_t i = 0; i < kRegs; ++i) qw[i] = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 64; ++i) {
+        const uint32_t c = i < rows ? sim_norm(s_valid, ld_char(nq, 64u * lane + i, cs), cs) : 0u;
+        if (kWide) qw[i] = c;
+        else qw[i >> 2] |= c << (8u * (i & 3u));
+    }
+    for (uint32_t r = 0; r < count; ++r) {
+        const uint32_t g = keys[r];
+        float best = kSimNone;
+        uint32_t best_t = kSimNoTerm;
+        uint32_t j = 0, je = 0, key = 0;
+        const SimMember& M = s_m[g < total ? set_member(s_m, P, g) : 0u];
+        if (g < total) {
+            key = g - M.base;
+            if (key < M.n_keys) key_terms(M, key, j, je);
+        }
+        for (; j < je; ++j) {
+            const uint32_t t = term_at(M, key, j);
+            if (t >= M.n_terms) continue;
+            const uint64_t ta = M.term_off[t];
+            const uint32_t L = (uint32_t)(M.term_off[t + 1] - ta);
+            if (!L) continue;
+            SimBlock<kMetric> b;
+            uint32_t score = m, low = m;
+            int hout = 0;
+            const uint32_t steps = L + W - 1u;
+            for (uint32_t s = 0; s < steps; ++s) {
+                const int up = __shfl_up(hout, 1);
+                int hin = lane == 0 ? kSimTopDelta<kMetric> : up;
+                uint32_t tin = 0, tout = 0;
+                if constexpr (kMetric == kSimOsa) {
+                    tin = lane == 0 ? 0u : (uint32_t)up >> 2;
+                    hin = lane == 0 ? +1 : (int)((uint32_t)up & 3u) - 1;
+                }
+                const uint32_t at = s - lane;
+                if (lane < W && at < L) {
+                    const uint32_t c = ld_char(M.term_bytes, ta + at, cs);
+                    uint64_t eq = 0;
+#pragma unroll
+                    for (uint32_t i = 0; i < 64; ++i) {
+                        const uint32_t qi = kWide ? qw[i] : (qw[i >> 2] >> (8u * (i & 3u))) & 255u;
+                        eq |= qi == c ? 1ull << i : 0ull;
+                    }
+                    hout = sim_step<kMetric>(b, eq & rowmask, hin, tin, top, tout);
+                    if (lane == W - 1u) sim_column<kMetric>(score, low, hout);
+                    if constexpr (kMetric == kSimOsa) hout = (hout + 1) | (int)(tout << 2);
+                }
+            }
+            const uint32_t d = (uint32_t)__shfl((int)(kMetric == kSimPartial ? low : score), (int)(W - 1u));
+            sim_take<kTerms>(best, best_t, sim_of<kMetric>(d, m, L), t);
+        }
+        if (lane == 0) {
+            out[r] = best;
+            if constexpr (kTerms) out_t[r] = best_t;
+        }
+    }
+}
+
 // ---- re-rank ----
 // One workgroup per query. Its size and its LDS follow the stride (launch_rerank): the sort runs over
 // n2 = the count rounded up to a power of two, n2 / 2 threads (64 .. kRerankThreads) make one
@@ -524,6 +775,41 @@ hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const u
     if (metric == kSimOsa) launch_sim_by_terms<kSimOsa>(X, A, s);
     else if (metric == kSimPartial) launch_sim_by_terms<kSimPartial>(X, A, s);
     else launch_sim_by_terms<kSimLevenshtein>(X, A, s);
+    return hipGetLastError();
+}
+
+namespace {
+template <uint32_t kMetric, bool kTerms>
+void launch_sim_set_as(const SimMembers& T, uint32_t P, uint32_t total, uint32_t cs, const SimArgs& A, hipStream_t s) {
+    if (cs == 4) hipLaunchKernelGGL((k_sim_set<true, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, T, P, total, A);
+    else hipLaunchKernelGGL((k_sim_set<false, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, T, P, total, A);
+}
+template <uint32_t kMetric>
+void launch_sim_set_by_terms(const SimMembers& T, uint32_t P, uint32_t total, uint32_t cs, const SimArgs& A,
+                             hipStream_t s) {
+    if (A.terms) launch_sim_set_as<kMetric, true>(T, P, total, cs, A, s);
+    else launch_sim_set_as<kMetric, false>(T, P, total, cs, A, s);
+}
+}  // namespace
+
+hipError_t launch_similarity_set(const SimMembers& T, uint32_t P, uint32_t cs, const uint32_t valid[8],
+                                 const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
+                                 const uint32_t* counts, const uint32_t* keys, uint32_t metric, float* sim,
+                                 uint32_t* terms, hipStream_t s) {
+    if (metric >= kSimMetrics || P == 0 || P > kSetMaxParts || (cs != 1 && cs != 4)) return hipErrorInvalidValue;
+    if (!n || !stride) return hipSuccess;
+    uint64_t total = 0;  // the members tile [0, total) in order
+    for (uint32_t p = 0; p < P; ++p) {
+        const SimMember& M = T.m[p];
+        if (M.base != total || (M.n_keys && !M.kt_off && !M.key_term)) return hipErrorInvalidValue;
+        total += M.n_keys;
+    }
+    if (total > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    SimArgs A{raw, off, counts, keys, sim, terms, nullptr, n, stride, {}};
+    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
+    if (metric == kSimOsa) launch_sim_set_by_terms<kSimOsa>(T, P, (uint32_t)total, cs, A, s);
+    else if (metric == kSimPartial) launch_sim_set_by_terms<kSimPartial>(T, P, (uint32_t)total, cs, A, s);
+    else launch_sim_set_by_terms<kSimLevenshtein>(T, P, (uint32_t)total, cs, A, s);
     return hipGetLastError();
 }
 

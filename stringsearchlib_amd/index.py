@@ -754,6 +754,128 @@ class IndexSet:
         _ok(_native.lib().ngsSetSearchDevice(self.set_id, d_bytes, d_offsets, n, threshold, limit, out_stride,
                                              d_counts, d_keys, d_scores, stream or None), "ngsSetSearchDevice")
 
+    # -- the later stages over the set (include/ngram_search.h): StringIndex's methods, global key ids --
+    def _stride(self, limit: int) -> int:
+        return max(1, min(limit if limit else INT32_MAX, self.num_keys()))
+
+    def term(self, key_id: int, term_id: int):
+        """The matched term `term_id` of a record whose key is the global `key_id`: term ids are local to
+        the member that holds the key."""
+        index, _ = self.locate(key_id)
+        return index.term(term_id)
+
+    def score_batch_sim(self, queries, threshold: float = 0.0, limit: int = 100, min_similarity: float = 0.0,
+                        metric=None, with_terms: bool = False, token_sort: bool = False):
+        """scoreBatchSetSimM / W / U8: StringIndex.score_batch_sim over the set. One list of (key, score, sim)
+        per query, with_terms (key, score, sim, term)."""
+        L, first = _native.lib(), self._parts[0]
+        what = "scoreBatchSetSimM" + first._fn["scoreBatch"][len("scoreBatch"):]
+        m = _metric("levenshtein" if metric is None else metric, token_sort)
+        nq = len(queries)
+        qs = first._queries(queries)
+        stride = self._stride(limit)
+        counts = (C.c_uint32 * max(1, nq))()
+        keys = (C.c_uint32 * max(1, nq * stride))()
+        scores = (C.c_float * max(1, nq * stride))()
+        sims = (C.c_float * max(1, nq * stride))()
+        terms = (C.c_uint32 * max(1, nq * stride))() if with_terms else None
+        L.ngsLastError(1)
+        total = getattr(L, what)(self.set_id, qs, nq, threshold, limit, m, min_similarity, stride, counts, keys, scores,
+                                 sims, terms)
+        if not total:
+            _check(what)
+        strings, names = {}, {}
+
+        def name(g):
+            if g not in strings:
+                strings[g] = self.key(g)
+            return strings[g]
+
+        def term(g, t):
+            if t == NO_TERM:
+                return None
+            index, _ = self.locate(g)
+            if (index.handle, t) not in names:
+                names[index.handle, t] = index.term(t)
+            return names[index.handle, t]
+
+        out = []
+        for i in range(nq):
+            at = range(i * stride, i * stride + counts[i])
+            out.append([(name(keys[j]), scores[j], sims[j]) + ((term(keys[j], terms[j]),) if with_terms else ())
+                        for j in at])
+        assert sum(map(len, out)) == total
+        return out
+
+    def self_join(self, first: int = 0, count: int | None = None, threshold: float = 0.0, limit: int = 10):
+        """selfJoinSet: StringIndex.self_join over the set's global key ids."""
+        L = _native.lib()
+        n = max(0, self.num_keys() - first) if count is None else count
+        stride = self._stride(limit)
+        counts = (C.c_uint32 * max(1, n))()
+        keys = (C.c_uint32 * max(1, n * stride))()
+        scores = (C.c_float * max(1, n * stride))()
+        L.ngsLastError(1)
+        total = L.selfJoinSet(self.set_id, first, n, threshold, limit, stride, counts, keys, scores)
+        if not total:
+            _check("selfJoinSet")
+        out = [list(zip(keys[i * stride:i * stride + counts[i]], scores[i * stride:i * stride + counts[i]]))
+               for i in range(n)]
+        assert sum(map(len, out)) == total
+        return out
+
+    def dedup(self, threshold: float, limit: int = 10, min_similarity: float | None = None, batch_keys: int = 0,
+              metric=None, token_sort: bool = False):
+        """dedupKeysSet: StringIndex.dedup over the set; labels[g] = the smallest global key id of key g's
+        cluster."""
+        L = _native.lib()
+        nk = self.num_keys()
+        labels = (C.c_uint32 * max(1, nk))()
+        L.ngsLastError(1)
+        ms = -1.0 if min_similarity is None else min_similarity
+        clusters = L.dedupKeysSet(self.set_id, threshold, limit, _metric("levenshtein" if metric is None else metric,
+                                                                          token_sort), ms, batch_keys, labels)
+        if not clusters:
+            _check("dedupKeysSet")
+        out = list(labels[:nk])
+        assert clusters == sum(1 for k, v in enumerate(out) if k == v)
+        return out
+
+    def similarity_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
+                          d_sim: int, stream: int = 0, metric=None, d_terms: int = 0, token_sort: bool = False) -> None:
+        """ngsSetSimilarityDeviceM on raw device pointers: StringIndex.similarity_device with global key ids;
+        d_terms receives the members' local term ids."""
+        _ok(_native.lib().ngsSetSimilarityDeviceM(
+            self.set_id, d_bytes, d_offsets, n, stride, d_counts, d_keys,
+            _metric("levenshtein" if metric is None else metric, token_sort), d_sim, d_terms or None, stream or None),
+            "ngsSetSimilarityDeviceM")
+
+    def rerank_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
+                      d_scores: int, d_sim: int, min_similarity: float = 0.0, stream: int = 0, metric=None,
+                      d_terms: int = 0, token_sort: bool = False) -> None:
+        """ngsSetRerankDeviceM on raw device pointers: StringIndex.rerank_device with global key ids."""
+        _ok(_native.lib().ngsSetRerankDeviceM(
+            self.set_id, d_bytes, d_offsets, n, stride, d_counts, d_keys, d_scores, d_sim, d_terms or None,
+            _metric("levenshtein" if metric is None else metric, token_sort), min_similarity, stream or None),
+            "ngsSetRerankDeviceM")
+
+    def key_query_bytes(self, first: int, count: int) -> int:
+        """ngsSetKeyQueryBytes: the bytes the global keys first .. first + count - 1 take as a query batch."""
+        return _native.lib().ngsSetKeyQueryBytes(self.set_id, first, count)
+
+    def key_queries_device(self, first: int, count: int, d_bytes: int, cap_bytes: int, d_offsets: int,
+                           stream: int = 0) -> None:
+        """ngsSetKeyQueriesDevice on raw device pointers: those keys in search_device's query layout."""
+        _ok(_native.lib().ngsSetKeyQueriesDevice(self.set_id, first, count, d_bytes or None, cap_bytes, d_offsets,
+                                                 stream or None), "ngsSetKeyQueriesDevice")
+
+    def self_join_device(self, first: int, count: int, threshold: float, limit: int, out_stride: int, d_counts: int,
+                         d_keys: int, d_scores: int, stream: int = 0) -> None:
+        """ngsSetSelfJoinDevice on raw device pointers; out_stride >= min((limit or 2^31-1) + 1, keys)."""
+        _ok(_native.lib().ngsSetSelfJoinDevice(self.set_id, first, count, threshold, limit, out_stride, d_counts,
+                                               d_keys or None, d_scores or None, stream or None),
+            "ngsSetSelfJoinDevice")
+
     def dispose(self) -> None:
         """Disposes the set; the members stay."""
         if self.set_id:
