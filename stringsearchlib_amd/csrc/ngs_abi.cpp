@@ -2507,36 +2507,71 @@ bool sim_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint3
     return d_off && d_n && !(n && stride && (!d_k || !d_v));
 }
 
+// What the similarity runs over: one index on a replica, or the members of an index set on the set's
+// device (sim_view, here and behind KeySet). A member's replica is null where it has none there.
+struct SimView {
+    struct Member {
+        Library* L;
+        Replica* R;
+        uint32_t base;
+    };
+    Member m[kSetMaxParts];
+    uint32_t P, csize;
+    bool set;  // launch_similarity_set, whatever P is
+};
+SimView sim_view(Library& L, Replica& R) { return {{{&L, &R, 0u}}, 1u, R.dev.csize, false}; }
+
 // Queues the similarity kernel by `metric` (and, with `rerank`, the re-rank behind it) on s; nothing
-// waits. d_t: the matched terms, or null. With kSimTokenSort in `metric` the kernel reads the
-// replica's token-sorted terms, and with d_sort (= d_raw, writable: the host calls' own scratch) the
-// queries are token-sorted in place in front of it, under the same snapshot of the validChar set;
-// without d_sort they are taken as given (the device entry points).
-int queue_similarity(Library& L, Replica& R, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
+// waits: -3 a member without a replica on the device, -4 a HIP failure. Every member's key_term map
+// (and with kSimTokenSort its token-sorted terms, which the kernel then reads) is built where
+// missing; the query is normalised under the first member's validChar set. d_t: the matched terms,
+// or null. With kSimTokenSort and d_sort (= d_raw, writable: the host calls' own scratch) the
+// queries are token-sorted in place in front of the kernel, under the same snapshot of the
+// validChar set; without d_sort they are taken as given (the device entry points). The view's
+// device is current.
+int queue_similarity(const SimView& V, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
                      uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, uint32_t* d_t, uint32_t metric, bool rerank,
                      float min_sim, hipStream_t s, uint8_t* d_sort = nullptr) {
     if (n == 0) return 0;
-    bool ok = true;
-    const uint32_t* key_term = sim_key_term(R, ok);
-    if (!ok) return -4;
+    const bool sorted = (metric & kSimTokenSort) != 0;
+    DevIndex X{};  // (a handle's: its one member's)
+    SimMembers T{};
+    for (uint32_t p = 0; p < V.P; ++p) {
+        Replica* R = V.m[p].R;
+        if (!R) return -3;
+        bool ok = true;
+        const uint32_t* key_term = sim_key_term(*R, ok);
+        if (!ok) return -4;
+        X = R->dev;
+        if (sorted && !sim_sorted_terms(*R, X)) return -4;
+        T.m[p] = SimMember{X.kt_off, X.kt_term, key_term, X.term_off, X.term_bytes, X.n_keys, X.n_terms, V.m[p].base, 0u};
+    }
     uint32_t valid[8];
     {
-        std::lock_guard<std::mutex> g(L.valid_mu);
-        std::memcpy(valid, L.valid, sizeof valid);
+        std::lock_guard<std::mutex> g(V.m[0].L->valid_mu);
+        std::memcpy(valid, V.m[0].L->valid, sizeof valid);
     }
-    if (metric & kSimTokenSort) {
-        DevIndex X = R.dev;
-        if (!sim_sorted_terms(R, X)) return -4;
-        if (d_sort && !HIP_CHECK(launch_token_sort(valid, X.csize, d_raw, d_off, n, d_sort, s))) return -4;
-        if (!HIP_CHECK(launch_similarity(X, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, sim_metric_base(metric),
-                                         d_v, d_t, s)))
-            return -4;
-    } else if (!HIP_CHECK(launch_similarity(R.dev, valid, key_term, d_raw, d_off, n, stride, d_n, d_k, metric, d_v, d_t,
-                                            s))) {
+    if (sorted && d_sort && !HIP_CHECK(launch_token_sort(valid, V.csize, d_raw, d_off, n, d_sort, s))) return -4;
+    const uint32_t base = sim_metric_base(metric);
+    if (!HIP_CHECK(V.set ? launch_similarity_set(T, V.P, V.csize, valid, d_raw, d_off, n, stride, d_n, d_k, base, d_v, d_t, s)
+                         : launch_similarity(X, valid, T.m[0].key_term, d_raw, d_off, n, stride, d_n, d_k, base, d_v, d_t, s)))
         return -4;
-    }
     if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
     return 0;
+}
+
+// ngsSimilarityDeviceM / ngsRerankDeviceM and their set forms behind the fronts that resolve the view
+// (the lock and the guards held): without and with the re-rank
+int similarity_entry(const SimView& V, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n, uint32_t stride,
+                     const uint32_t* d_n, const uint32_t* d_k, uint32_t metric, float* d_v, uint32_t* d_t, void* stream) {
+    return queue_similarity(V, d_raw, d_off, n, stride, const_cast<uint32_t*>(d_n), const_cast<uint32_t*>(d_k), nullptr,
+                            d_v, d_t, metric, false, 0.0f, (hipStream_t)stream);
+}
+// the argument checks of the re-rank entry points, in front of their fronts
+bool rerank_args_ok(const uint64_t* d_off, uint32_t n, uint32_t stride, const uint32_t* d_n, const uint32_t* d_k,
+                    const float* d_s, const float* d_v, uint32_t metric, float min_sim) {
+    return sim_args_ok(d_off, n, stride, d_n, d_k, d_v) && !(n && stride && !d_s) && stride <= kRerankMaxStride &&
+           min_sim == min_sim && sim_metric_ok(metric);
 }
 
 // The device entry points' front, in two halves (the caller holds the lock; each entry point puts
@@ -2590,6 +2625,41 @@ struct CallScratch {
 };
 constexpr size_t kSimChunkRecords = size_t(1) << 22;  // records (query x limit) per chunk of a scoreBatchSim* call
 
+// The queries of a host call as they go up, `chunk` at a time: every query's bytes and their number,
+// and the bytes of the largest chunk (raw_cap), so that the device buffers are made once.
+struct QueryChunks {
+    uint32_t chunk;
+    std::vector<const uint8_t*> ptr;
+    std::vector<size_t> bytes;
+    size_t raw_cap = 0;
+    std::vector<uint64_t> h_off;
+    std::vector<uint8_t> h_raw;
+    // bytes_of(i, n): query i's bytes, n their number
+    template <class F>
+    QueryChunks(uint32_t nq, uint32_t chunk_, F&& bytes_of) : chunk(chunk_), ptr(nq), bytes(nq), h_off((size_t)chunk_ + 1) {
+        for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+            size_t sum = 0;
+            for (uint32_t i = q0; i < q0 + std::min(chunk, nq - q0); ++i) {
+                ptr[i] = static_cast<const uint8_t*>(bytes_of(i, bytes[i]));
+                sum += bytes[i];
+            }
+            raw_cap = std::max(raw_cap, sum);
+        }
+    }
+    // queries [q0, q0 + B) packed behind one another, their B + 1 byte offsets and their bytes queued
+    // for d_off / d_raw on s (the host copies stay valid until the next chunk is packed)
+    bool upload(uint32_t q0, uint32_t B, uint64_t* d_off, uint8_t* d_raw, hipStream_t s) {
+        h_raw.clear();
+        h_off[0] = 0;
+        for (uint32_t i = 0; i < B; ++i) {
+            if (bytes[q0 + i]) h_raw.insert(h_raw.end(), ptr[q0 + i], ptr[q0 + i] + bytes[q0 + i]);
+            h_off[i + 1] = h_raw.size();
+        }
+        return HIP_CHECK(hipMemcpyAsync(d_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice, s)) &&
+               (h_raw.empty() || HIP_CHECK(hipMemcpyAsync(d_raw, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, s)));
+    }
+};
+
 // scoreBatchSim / scoreBatchSimW / scoreBatchSimU8, plainly on top of the device stages: the
 // queries packed and uploaded, the search as ngsSearchDevice runs it, ngsRerankDevice's kernels
 // behind it on the same stream, then counts, key ids, scores and sims read back and the result
@@ -2624,58 +2694,32 @@ uint32_t sim_batch(uint32_t handle, const CharT* const* queries, uint32_t nq, fl
     // 1. the queries as the device entry points take them: characters of cs bytes, byte offsets
     DecodedStrings D;
     if (u8) decode_strings(reinterpret_cast<const char* const*>(queries), nq, D);
-    auto chars_of = [&](uint32_t i, size_t& len) -> const void* {
+    const uint32_t chunk = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, kSimChunkRecords / Lm));
+    QueryChunks Q(nq, chunk, [&](uint32_t i, size_t& bytes) -> const void* {
         if (u8) {
-            len = D.ptr[i] ? str_len(D.ptr[i]) : 0;
+            bytes = D.ptr[i] ? str_len(D.ptr[i]) * cs : 0;
             return D.ptr[i];
         }
-        len = queries[i] ? str_len(queries[i]) : 0;
+        bytes = queries[i] ? str_len(queries[i]) * cs : 0;
         return queries[i];
-    };
-    // every query's characters and length, and the bytes of the largest chunk: the device buffers
-    // are made once, before the loop
-    const uint32_t chunk = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, kSimChunkRecords / Lm));
-    std::vector<const uint8_t*> q_ptr(nq);
-    std::vector<size_t> q_len(nq);
-    size_t raw_cap = 0;
-    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
-        size_t bytes = 0;
-        for (uint32_t i = q0; i < q0 + std::min(chunk, nq - q0); ++i) {
-            q_ptr[i] = static_cast<const uint8_t*>(chars_of(i, q_len[i]));
-            bytes += q_len[i] * cs;
-        }
-        raw_cap = std::max(raw_cap, bytes);
-    }
+    });
     CallScratch M;
     uint32_t* d_t = nullptr;
     float* d_v = nullptr;
     const size_t recs = (size_t)chunk * Lm;
-    if (!M.begin(chunk, Lm, raw_cap) || !M.alloc(&d_v, recs) || (terms && !M.alloc(&d_t, recs))) return 0;
+    if (!M.begin(chunk, Lm, Q.raw_cap) || !M.alloc(&d_v, recs) || (terms && !M.alloc(&d_t, recs))) return 0;
     std::vector<uint32_t> cnt(nq, 0), keys, h_n(chunk), h_k(recs);  // (counts stay zero unless the whole call succeeds)
     std::vector<uint32_t> tv, h_t(terms ? recs : 0);
     std::vector<float> sc, sv, h_s(recs), h_v(recs);
-    std::vector<uint64_t> h_off((size_t)chunk + 1);
-    std::vector<uint8_t> h_raw;
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t B = std::min(chunk, nq - q0);
-        h_raw.clear();
-        h_off[0] = 0;
-        for (uint32_t i = 0; i < B; ++i) {
-            const uint8_t* p = q_ptr[q0 + i];
-            if (q_len[q0 + i]) h_raw.insert(h_raw.end(), p, p + q_len[q0 + i] * cs);
-            h_off[i + 1] = h_raw.size();
-        }
-        if (!HIP_CHECK(hipMemcpyAsync(M.d_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice,
-                                      M.stream)) ||
-            (!h_raw.empty() &&
-             !HIP_CHECK(hipMemcpyAsync(M.d_raw, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, M.stream))))
-            return 0;
+        if (!Q.upload(q0, B, M.d_off, M.d_raw, M.stream)) return 0;
         // 2. the search, 3. the re-rank behind it
         if (search_on_replica(*L, R, M.d_raw, M.d_off, B, thr, Lm, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0) {
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (queue_similarity(*L, R, M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, metric, true, min_sim,
+        if (queue_similarity(sim_view(*L, R), M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, metric, true, min_sim,
                              M.stream, M.d_raw) != 0)
             return 0;
         // 4. everything back
@@ -2769,7 +2813,7 @@ struct OneJoin {
     }
     // the batch's similarities into d_v (the gathered queries token-sorted in place when flagged)
     int similarity(CallScratch& M, uint32_t n, uint32_t stride, float* d_v, uint32_t metric) {
-        return queue_similarity(L, R, M.d_raw, M.d_off, n, stride, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric, false,
+        return queue_similarity(sim_view(L, R), M.d_raw, M.d_off, n, stride, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric, false,
                                 0.0f, M.stream, M.d_raw);
     }
 };
@@ -2961,7 +3005,7 @@ uint32_t link_host(uint32_t h_from, uint32_t h_to, float thr, uint32_t limit, ui
             if (!t_last_error) t_last_error = kErrInternal;
             return 0;
         }
-        if (verify && (queue_similarity(*T, R, M.d_raw, M.d_off, n, Ls, d_n, d_k, d_s, d_sim, nullptr, metric, false,
+        if (verify && (queue_similarity(sim_view(*T, R), M.d_raw, M.d_off, n, Ls, d_n, d_k, d_s, d_sim, nullptr, metric, false,
                                         0.0f, M.stream, M.d_raw) != 0 ||
                        !HIP_CHECK(launch_keep_similar(d_n, d_k, d_s, d_sim, n, Ls, min_sim, M.stream, d_sim))))
             return 0;
@@ -3143,37 +3187,11 @@ int set_device_current(const KeySet& S) {
     return cur == S.device ? 0 : -3;
 }
 
-// queue_similarity over a set: every member's key_term map (and with kSimTokenSort its sorted terms)
-// built where missing, as the single-index path builds them, then one launch of k_sim_set for the
-// whole block, under the first member's validChar set. The set's device is current.
-int queue_set_similarity(const KeySet& S, Library* const* libs, const uint8_t* d_raw, const uint64_t* d_off, uint32_t n,
-                         uint32_t stride, uint32_t* d_n, uint32_t* d_k, float* d_s, float* d_v, uint32_t* d_t,
-                         uint32_t metric, bool rerank, float min_sim, hipStream_t s, uint8_t* d_sort = nullptr) {
-    if (n == 0) return 0;
-    SimMembers T{};
-    for (size_t p = 0; p < S.parts.size(); ++p) {
-        Replica* R = libs[p]->replica_at(S.device);
-        if (!R) return -3;
-        bool ok = true;
-        const uint32_t* key_term = sim_key_term(*R, ok);
-        if (!ok) return -4;
-        DevIndex X = R->dev;
-        if ((metric & kSimTokenSort) && !sim_sorted_terms(*R, X)) return -4;
-        T.m[p] = SimMember{X.kt_off, X.kt_term, key_term, X.term_off, X.term_bytes, X.n_keys, X.n_terms,
-                           S.parts[p].base, 0u};
-    }
-    uint32_t valid[8];
-    {
-        std::lock_guard<std::mutex> g(libs[0]->valid_mu);
-        std::memcpy(valid, libs[0]->valid, sizeof valid);
-    }
-    if ((metric & kSimTokenSort) && d_sort && !HIP_CHECK(launch_token_sort(valid, S.csize, d_raw, d_off, n, d_sort, s)))
-        return -4;
-    if (!HIP_CHECK(launch_similarity_set(T, (uint32_t)S.parts.size(), S.csize, valid, d_raw, d_off, n, stride, d_n, d_k,
-                                         sim_metric_base(metric), d_v, d_t, s)))
-        return -4;
-    if (rerank && !HIP_CHECK(launch_rerank(n, stride, d_n, d_k, d_s, d_v, d_t, min_sim, s))) return -4;
-    return 0;
+// the similarity's view of a set: its members on the set's device, one launch of k_sim_set for a block
+SimView sim_view(const KeySet& S, Library* const* libs) {
+    SimView V{{}, (uint32_t)S.parts.size(), S.csize, true};
+    for (uint32_t p = 0; p < V.P; ++p) V.m[p] = {libs[p], libs[p]->replica_at(S.device), S.parts[p].base};
+    return V;
 }
 
 // f(p, local first key, keys, position in the range) for every member holding keys of the global
@@ -3256,7 +3274,7 @@ struct SetJoin {
                               false);
     }
     int similarity(CallScratch& M, uint32_t n, uint32_t stride, float* d_v, uint32_t metric) {
-        return queue_set_similarity(S, libs, M.d_raw, M.d_off, n, stride, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric, false,
+        return queue_similarity(sim_view(S, libs), M.d_raw, M.d_off, n, stride, M.d_n, M.d_k, M.d_s, d_v, nullptr, metric, false,
                                     0.0f, M.stream, M.d_raw);
     }
 };
@@ -3302,16 +3320,11 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
     const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1, kSimChunkRecords / per_query));
     // every query's bytes as they go up (u8: the UTF-8 bytes), and the bytes of the largest chunk
     const uint32_t up = u8 ? 1u : cs;  // bytes per unit of what is uploaded
-    std::vector<size_t> q_len(nq);
-    size_t raw_cap = 0;
-    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
-        size_t bytes = 0;
-        for (uint32_t i = q0; i < q0 + std::min(chunk, nq - q0); ++i) {
-            q_len[i] = queries[i] ? str_len(queries[i]) : 0;
-            bytes += q_len[i] * up;
-        }
-        raw_cap = std::max(raw_cap, bytes);
-    }
+    QueryChunks Q(nq, chunk, [&](uint32_t i, size_t& bytes) -> const void* {
+        bytes = queries[i] ? str_len(queries[i]) * up : 0;
+        return queries[i];
+    });
+    const size_t raw_cap = Q.raw_cap;
     CallScratch M;
     SetBlocks K;
     uint8_t *d_u8 = nullptr, *d_u8temp = nullptr;
@@ -3326,30 +3339,16 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
         return fail(0);
     std::vector<uint32_t> h_n(chunk), h_k(recs), h_t(d_t ? recs : 0);
     std::vector<float> h_s(recs), h_v(sim ? recs : 0);
-    std::vector<uint64_t> h_off((size_t)chunk + 1);
-    std::vector<uint8_t> h_raw;
     uint64_t total = 0;
     for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
         const uint32_t B = std::min(chunk, nq - q0);
-        h_raw.clear();
-        h_off[0] = 0;
-        for (uint32_t i = 0; i < B; ++i) {
-            const uint8_t* p = reinterpret_cast<const uint8_t*>(queries[q0 + i]);
-            if (q_len[q0 + i]) h_raw.insert(h_raw.end(), p, p + q_len[q0 + i] * up);
-            h_off[i + 1] = h_raw.size();
-        }
-        uint8_t* d_in = u8 ? d_u8 : M.d_raw;
-        uint64_t* d_in_off = u8 ? d_u8off : M.d_off;
-        if (!HIP_CHECK(hipMemcpyAsync(d_in_off, h_off.data(), sizeof(uint64_t) * (B + 1), hipMemcpyHostToDevice,
-                                      M.stream)) ||
-            (!h_raw.empty() &&
-             !HIP_CHECK(hipMemcpyAsync(d_in, h_raw.data(), h_raw.size(), hipMemcpyHostToDevice, M.stream))) ||
+        if (!Q.upload(q0, B, u8 ? d_u8off : M.d_off, u8 ? d_u8 : M.d_raw, M.stream) ||
             (u8 && !HIP_CHECK(launch_utf8_decode(d_u8, d_u8off, B, reinterpret_cast<uint32_t*>(M.d_raw), raw_cap,
                                                  M.d_off, d_u8temp, u8temp, M.stream))))
             return fail(0);
         if (set_search(*S, libs, K, M.d_raw, M.d_off, B, thr, limit, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0)
             return fail(kErrInternal);
-        if (sim && queue_set_similarity(*S, libs, M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, sim->metric, true,
+        if (sim && queue_similarity(sim_view(*S, libs), M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, sim->metric, true,
                                         sim->min_sim, M.stream, M.d_raw) != 0)
             return fail(kErrInternal);
         const size_t rb = (size_t)B * Lm;
@@ -3869,25 +3868,22 @@ NGS_API int ngsSimilarityDeviceM(uint32_t handle, const uint8_t* dQueryBytes, co
     if (const int rc = entry_library(handle, L)) return rc;
     if (const int rc = entry_replica(*L, R)) return rc;
     BatchGuard bg(L);
-    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
-                            const_cast<uint32_t*>(dKeys), nullptr, dSim, dTerms, metric, false, 0.0f,
-                            (hipStream_t)stream);
+    return similarity_entry(sim_view(*L, *R), dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, metric, dSim,
+                            dTerms, stream);
 }
 
 NGS_API int ngsRerankDeviceM(uint32_t handle, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
                              uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
                              float* dSim, uint32_t* dTerms, uint32_t metric, float minSimilarity, void* stream) {
-    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
-        stride > kRerankMaxStride || minSimilarity != minSimilarity || !sim_metric_ok(metric))
-        return -3;
+    if (!rerank_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, metric, minSimilarity)) return -3;
     std::shared_lock<std::shared_mutex> lk(g_lock);
     Library* L = nullptr;
     Replica* R = nullptr;
     if (const int rc = entry_library(handle, L)) return rc;
     if (const int rc = entry_replica(*L, R)) return rc;
     BatchGuard bg(L);
-    return queue_similarity(*L, *R, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, dTerms,
-                            metric, true, minSimilarity, (hipStream_t)stream);
+    return queue_similarity(sim_view(*L, *R), dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim,
+                            dTerms, metric, true, minSimilarity, (hipStream_t)stream);
 }
 
 NGS_API uint32_t scoreBatchSimM(uint32_t handle, const char* const* queries, uint32_t nQueries, float threshold,
@@ -4171,25 +4167,22 @@ NGS_API int ngsSetSimilarityDeviceM(uint32_t set, const uint8_t* dQueryBytes, co
     if (const int rc = entry_set(set, S, libs)) return rc;
     if (const int rc = set_device_current(*S)) return rc;
     SetGuards guards(*S, libs);
-    return queue_set_similarity(*S, libs, dQueryBytes, dQueryOffsets, nQueries, stride, const_cast<uint32_t*>(dCounts),
-                                const_cast<uint32_t*>(dKeys), nullptr, dSim, dTerms, metric, false, 0.0f,
-                                (hipStream_t)stream);
+    return similarity_entry(sim_view(*S, libs), dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, metric, dSim,
+                            dTerms, stream);
 }
 
 NGS_API int ngsSetRerankDeviceM(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
                                 uint32_t nQueries, uint32_t stride, uint32_t* dCounts, uint32_t* dKeys, float* dScores,
                                 float* dSim, uint32_t* dTerms, uint32_t metric, float minSimilarity, void* stream) {
-    if (!sim_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dSim) || (nQueries && stride && !dScores) ||
-        stride > kRerankMaxStride || minSimilarity != minSimilarity || !sim_metric_ok(metric))
-        return -3;
+    if (!rerank_args_ok(dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim, metric, minSimilarity)) return -3;
     std::shared_lock<std::shared_mutex> lk(g_lock);
     KeySet* S = nullptr;
     Library* libs[kSetMaxParts] = {};
     if (const int rc = entry_set(set, S, libs)) return rc;
     if (const int rc = set_device_current(*S)) return rc;
     SetGuards guards(*S, libs);
-    return queue_set_similarity(*S, libs, dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim,
-                                dTerms, metric, true, minSimilarity, (hipStream_t)stream);
+    return queue_similarity(sim_view(*S, libs), dQueryBytes, dQueryOffsets, nQueries, stride, dCounts, dKeys, dScores, dSim,
+                            dTerms, metric, true, minSimilarity, (hipStream_t)stream);
 }
 
 NGS_API uint64_t ngsSetKeyQueryBytes(uint32_t set, uint32_t firstKey, uint32_t nKeys) {

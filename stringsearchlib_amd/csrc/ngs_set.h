@@ -130,18 +130,8 @@ inline uint64_t merge_min_stride(const MergePart* parts, uint32_t P, uint32_t li
 // The query is normalised once, with the validChar set of the set's first member: a caller who
 // changes one member's set changes them all (§9.7).
 //
-// One member as k_sim_set takes it, by value: its key -> terms arrays (kt_off / kt_term, or key_term
-// where every key has one pair: kt_off null) and its terms (term_off / term_bytes, or the
-// token-sorted pair). Members of both storage forms mix in one launch.
-struct SimMember {
-    const uint32_t* kt_off;
-    const uint32_t* kt_term;
-    const uint32_t* key_term;
-    const uint64_t* term_off;
-    const uint8_t* term_bytes;
-    uint32_t n_keys, n_terms, base, pad;
-};
-static_assert(sizeof(SimMember) == 56, "16 members x 56 bytes travel in the kernel arguments");
+// The members as k_sim_set takes them, by value (ngs_sim.h: SimMember); members of both storage
+// forms mix in one launch.
 struct SimMembers {
     SimMember m[kSetMaxParts];
 };

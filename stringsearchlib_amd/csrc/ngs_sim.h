@@ -261,6 +261,21 @@ inline uint32_t partial_myers_blocks(QF q, uint32_t m, TF t, uint32_t L) {
     return best;
 }
 
+// ---- the similarity's view of an index ----
+// What the kernels read of one index: its key -> terms arrays (kt_off / kt_term, or key_term where
+// every key has one pair: kt_off null) and its terms (term_off / term_bytes, or the token-sorted
+// pair). `base` is the first key id the index owns: 0 for a single index, the member's base in an
+// index set (ngs_set.h), whose members travel by value in the kernel arguments.
+struct SimMember {
+    const uint32_t* kt_off;
+    const uint32_t* kt_term;
+    const uint32_t* key_term;
+    const uint64_t* term_off;
+    const uint8_t* term_bytes;
+    uint32_t n_keys, n_terms, base, pad;
+};
+static_assert(sizeof(SimMember) == 56, "16 members x 56 bytes travel in the kernel arguments");
+
 // ---- the wide short path's match-mask table: open addressing over kSimSlots slots ----
 constexpr uint32_t kSimSlots = 128;            // <= 64 distinct characters: at most half full
 constexpr uint32_t kSimEmpty = 0xFFFFFFFFu;    // no normalised character (they are <= 0x10FFFF)

@@ -1,8 +1,9 @@
 // ngs_sim.hip — the verification stage behind the search: the edit-distance
 // similarity of every (query, key) record of a result block, and the re-rank by it, for gfx950.
 //
-// k_sim: one wave per query. The wave normalises the query as k_prep does (ballot windows find
-// the trim), then takes one of two wave-uniform paths by the normalised length m:
+// sim_wave: one wave per query, the body of both similarity kernels. The wave normalises the query
+// as k_prep does (ballot windows find the trim), then takes one of two wave-uniform paths by the
+// normalised length m:
 //   m <= 64   lanes are records: the query's match masks go to LDS once, and every lane follows
 //             key -> term -> term_off -> term_bytes and streams its term through the one-word global
 //             Myers recurrence (ngs_sim.h: myers_step with hin = +1);
@@ -11,9 +12,11 @@
 //             one step earlier.
 // k_rerank: one workgroup per query sorts (sim desc, position asc) in LDS and permutes in place.
 // The metric (ngs_sim.h: Levenshtein, OSA, partial) and the matched-term output are template
-// parameters of k_sim, the term array one of k_rerank: launch_similarity and
-// launch_rerank pick the instantiation; the entry points without a metric are kSimLevenshtein, no terms.
-// k_sim_set: k_sim over an index set, the member of every record looked up in the wave.
+// parameters of the body, the term array one of k_rerank: the launch functions pick
+// the instantiation; the entry points without a metric are kSimLevenshtein, no terms.
+// The body takes the arrays behind a key id from a source, and each source has its
+// kernel: k_sim, one index held in registers, and k_sim_set, an index set whose member of every
+// record is looked up in the wave, in a table in LDS.
 #include <hip/hip_runtime.h>
 
 #include "ngs_common.h"
@@ -39,19 +42,42 @@ __device__ __forceinline__ uint32_t ld_char(const uint8_t* base, uint64_t i, uin
     return cs == 4 ? reinterpret_cast<const uint32_t*>(base)[i] : (uint32_t)base[i];
 }
 
-// the terms of key `key`: [j, je) of kt_term, or the one term of key_term (j = 0, je = 1)
-__device__ __forceinline__ void key_terms(const DevIndex& X, uint32_t key, uint32_t& j, uint32_t& je) {
-    if (X.kt_off) {
-        j = X.kt_off[key];
-        je = X.kt_off[key + 1];
+// the terms of M's local key `key`: [j, je) of kt_term, or the one term of key_term (j = 0, je = 1)
+__device__ __forceinline__ void key_terms(const SimMember& M, uint32_t key, uint32_t& j, uint32_t& je) {
+    if (M.kt_off) {
+        j = M.kt_off[key];
+        je = M.kt_off[key + 1];
     } else {
         j = 0;
         je = 1;
     }
 }
-__device__ __forceinline__ uint32_t term_at(const DevIndex& X, const uint32_t* key_term, uint32_t key, uint32_t j) {
-    return X.kt_off ? X.kt_term[j] : key_term[key];
+__device__ __forceinline__ uint32_t term_at(const SimMember& M, uint32_t key, uint32_t j) {
+    return M.kt_off ? M.kt_term[j] : M.key_term[key];
 }
+
+// Where a key id's arrays come from: total key ids, member(g) the index owning g < total, at(p) its
+// arrays with the first key id it owns. One index is a SimMember in registers: nothing is looked up,
+// and its base of 0 and the member index fold away.
+struct OneIndex {
+    SimMember M;
+    uint32_t total;
+    __device__ __forceinline__ uint32_t member(uint32_t) const { return 0; }
+    __device__ __forceinline__ const SimMember& at(uint32_t) const { return M; }
+};
+// An index set: the members' descriptors in LDS, so that lanes in different members
+// index them without a trip to memory. Their bases ascend from 0: the owner of g is the last member
+// whose base is at or below it. Members with kt_off / kt_term and with the key_term map mix freely.
+struct IndexSet {
+    const SimMember* m;
+    uint32_t P, total;
+    __device__ __forceinline__ uint32_t member(uint32_t g) const {
+        uint32_t p = 0;
+        for (uint32_t i = 1; i < P; ++i) p += m[i].base <= g ? 1u : 0u;
+        return p;
+    }
+    __device__ __forceinline__ const SimMember& at(uint32_t p) const { return m[p]; }
+};
 
 // The recurrence's state and one column of it by metric (ngs_sim.h): kSimOsa carries two more words
 // and the transposition bit between blocks; kSimPartial is the Levenshtein step behind hin = 0.
@@ -143,8 +169,11 @@ __device__ __forceinline__ void sim_take(float& best, uint32_t& best_t, float v,
     }
 }
 
-template <bool kWide, uint32_t kMetric = kSimLevenshtein, bool kTerms = false>
-__global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
+// One wave's work on query blockIdx.x, for both kernels: everything but where a key id's arrays
+// come from, which is `src`. The barrier behind s_valid also orders what the caller wrote to LDS
+// before the call (k_sim_set's member table).
+template <bool kWide, uint32_t kMetric, bool kTerms, class Src>
+__device__ __forceinline__ void sim_wave(const Src& src, const SimArgs& A) {
     constexpr uint32_t cs = kWide ? 4u : 1u;
     __shared__ uint64_t s_mask[256];             // narrow: by byte; wide: slots [0, kSimSlots)
     __shared__ uint32_t s_key[kSimSlots];        // wide: the slots' characters
@@ -232,265 +261,18 @@ __global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
         }
         __syncthreads();
 
-        // rounds of 64 records; the next round's key -> term -> offsets chain is issued before
-        // the current round's recurrence
-        uint32_t key = lane < count ? keys[lane] : kSimEmpty;
-        uint32_t j = 0, je = 0, tt = kSimNoTerm;  // tt: the term [ta, tb) belongs to (read with kTerms)
-        uint64_t ta = 0, tb = 0;
-        auto first_term = [&](uint32_t k, uint32_t& fj, uint32_t& fje, uint64_t& fa, uint64_t& fb, uint32_t& ft) {
-            fj = fje = 0;
-            fa = fb = 0;
-            ft = kSimNoTerm;
-            if (k >= X.n_keys) return;
-            key_terms(X, k, fj, fje);
-            if (fj >= fje) return;
-            const uint32_t t = term_at(X, A.key_term, k, fj);
-            if (t >= X.n_terms) return;
-            ft = t;
-            fa = X.term_off[t];
-            fb = X.term_off[t + 1];
-        };
-        first_term(key, j, je, ta, tb, tt);
-        for (uint32_t base = 0; base < count; base += 64) {
-            const uint32_t r = base + lane, rn = r + 64;
-            const uint32_t nkey = rn < count ? keys[rn] : kSimEmpty;
-            uint32_t nj, nje, nt;
-            uint64_t na, nb;
-            first_term(nkey, nj, nje, na, nb, nt);
-            float best = kSimNone;
-            uint32_t best_t = kSimNoTerm;
-            while (j < je) {
-                if (tb > ta) {
-                    const uint32_t L = (uint32_t)(tb - ta);
-                    uint32_t d = kMetric == kSimPartial ? 0u : L;  // an empty Q: L insertions (partial: none)
-                    if (m) {
-                        if (kWide)
-                            d = myers_wide<kMetric>(s_mask, s_key, m, reinterpret_cast<const uint32_t*>(X.term_bytes) + ta, L);
-                        else d = myers_narrow<kMetric>(s_mask, m, X.term_bytes, ta, L);
-                    }
-                    sim_take<kTerms>(best, best_t, sim_of<kMetric>(d, m, L), tt);
-                }
-                if (++j < je) {
-                    const uint32_t t = term_at(X, A.key_term, key, j);
-                    ta = tb = 0;
-                    if (t < X.n_terms) {
-                        tt = t;
-                        ta = X.term_off[t];
-                        tb = X.term_off[t + 1];
-                    }
-                }
-            }
-            if (r < count) {
-                out[r] = best;
-                if constexpr (kTerms) out_t[r] = best_t;
-            }
-            key = nkey;
-            j = nj;
-            je = nje;
-            ta = na;
-            tb = nb;
-            tt = nt;
-        }
-        return;
-    }
-
-    // ---- long path: the wave is a systolic pipeline over the query's W words ----
-    const uint32_t W = (m + 63u) / 64u;
-    const uint32_t rows = lane + 1u < W ? 64u : (lane < W ? m - 64u * lane : 0u);
-    const uint64_t top = rows ? 1ull << (rows - 1u) : 0ull;
-    const uint64_t rowmask = rows == 64u ? ~0ull : (1ull << rows) - 1ull;
-    // this lane's 64 query characters: bytes packed four to a register, or one register each
-    constexpr uint32_t kRegs = kWide ? 64u : 16u;
-    uint32_t qw[kRegs];
-#pragma unroll
-    for (uint32_t i = 0; i < kRegs; ++i) qw[i] = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < 64; ++i) {
-        const uint32_t c = i < rows ? sim_norm(s_valid, ld_char(nq, 64u * lane + i, cs), cs) : 0u;
-        if (kWide) qw[i] = c;
-        else qw[i >> 2] |= c << (8u * (i & 3u));
-    }
-    for (uint32_t r = 0; r < count; ++r) {
-        const uint32_t key = keys[r];
-        float best = kSimNone;
-        uint32_t best_t = kSimNoTerm;
-        uint32_t j = 0, je = 0;
-        if (key < X.n_keys) key_terms(X, key, j, je);
-        for (; j < je; ++j) {
-            const uint32_t t = term_at(X, A.key_term, key, j);
-            if (t >= X.n_terms) continue;
-            const uint64_t ta = X.term_off[t];
-            const uint32_t L = (uint32_t)(X.term_off[t + 1] - ta);
-            if (!L) continue;
-            SimBlock<kMetric> b;
-            uint32_t score = m, low = m;  // followed by lane W - 1
-            int hout = 0;  // kSimOsa: the transposition bit rides in bit 2 of hout + 1
-            const uint32_t steps = L + W - 1u;
-            for (uint32_t s = 0; s < steps; ++s) {
-                // lane w is at term character s - w, with the delta lane w - 1 left at it one step ago
-                const int up = __shfl_up(hout, 1);
-                int hin = lane == 0 ? kSimTopDelta<kMetric> : up;
-                uint32_t tin = 0, tout = 0;
-                if constexpr (kMetric == kSimOsa) {
-                    tin = lane == 0 ? 0u : (uint32_t)up >> 2;
-                    hin = lane == 0 ? +1 : (int)((uint32_t)up & 3u) - 1;
-                }
-                const uint32_t at = s - lane;
-                if (lane < W && at < L) {  // (s < lane wraps past L)
-                    const uint32_t c = ld_char(X.term_bytes, ta + at, cs);
-                    uint64_t eq = 0;
-#pragma unroll
-                    for (uint32_t i = 0; i < 64; ++i) {
-                        const uint32_t qi = kWide ? qw[i] : (qw[i >> 2] >> (8u * (i & 3u))) & 255u;
-                        eq |= qi == c ? 1ull << i : 0ull;
-                    }
-                    hout = sim_step<kMetric>(b, eq & rowmask, hin, tin, top, tout);
-                    if (lane == W - 1u) sim_column<kMetric>(score, low, hout);
-                    if constexpr (kMetric == kSimOsa) hout = (hout + 1) | (int)(tout << 2);
-                }
-            }
-            const uint32_t d = (uint32_t)__shfl((int)(kMetric == kSimPartial ? low : score), (int)(W - 1u));
-            sim_take<kTerms>(best, best_t, sim_of<kMetric>(d, m, L), t);
-        }
-        if (lane == 0) {
-            out[r] = best;
-            if constexpr (kTerms) out_t[r] = best_t;
-        }
-    }
-}
-
-// ---- the similarity over an index set ----
-// k_sim with the index looked up per record: a key id is global, the member owning it comes from a
-// count over the members' ascending bases (set_member), and every later step of the chain key ->
-// term -> term_off -> term_bytes goes through that member's descriptor. The descriptors travel by
-// value in the kernel arguments and are copied to LDS once, so that lanes in different members
-// index them without a trip to memory; a lane carries its member's index beside its key. Members
-// with kt_off / kt_term and members with the key_term map mix freely. The matched term is the
-// member's local term id. Everything about the query (wildcard, trim, masks, the systolic words)
-// is k_sim's, as are the recurrences.
-__device__ __forceinline__ uint32_t set_member(const SimMember* m, uint32_t P, uint32_t g) {
-    uint32_t p = 0;  // bases ascend from 0: the last member whose base is at or below g
-    for (uint32_t i = 1; i < P; ++i) p += m[i].base <= g ? 1u : 0u;
-    return p;
-}
-__device__ __forceinline__ void key_terms(const SimMember& M, uint32_t key, uint32_t& j, uint32_t& je) {
-    if (M.kt_off) {
-        j = M.kt_off[key];
-        je = M.kt_off[key + 1];
-    } else {
-        j = 0;
-        je = 1;
-    }
-}
-__device__ __forceinline__ uint32_t term_at(const SimMember& M, uint32_t key, uint32_t j) {
-    return M.kt_off ? M.kt_term[j] : M.key_term[key];
-}
-
-template <bool kWide, uint32_t kMetric, bool kTerms>
-__global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32_t total, SimArgs A) {
-    constexpr uint32_t cs = kWide ? 4u : 1u;
-    __shared__ uint64_t s_mask[256];
-    __shared__ uint32_t s_key[kSimSlots];
-    __shared__ uint32_t s_valid[8];
-    __shared__ SimMember s_m[kSetMaxParts];
-    const uint32_t lane = threadIdx.x, q = blockIdx.x;
-    if (lane < 8) s_valid[lane] = A.V.w[lane];
-    if (lane == 0) {
-#pragma unroll
-        for (uint32_t p = 0; p < kSetMaxParts; ++p)
-            if (p < P) s_m[p] = T.m[p];  // (constant indexes: scalar loads; entries from P on are never read)
-    }
-    __syncthreads();
-
-    const uint32_t count = min(A.counts[q], A.stride);
-    if (count == 0) return;
-    const uint32_t* keys = A.keys + (size_t)q * A.stride;
-    float* out = A.sim + (size_t)q * A.stride;
-    uint32_t* out_t = kTerms ? A.terms + (size_t)q * A.stride : nullptr;
-    const uint64_t qa = A.off[q], qe = A.off[q + 1];
-    const uint64_t n = qe > qa ? (qe - qa) / cs : 0;
-    const uint8_t* rq = A.raw + qa;
-
-    float fixed = 0.0f;
-    bool is_fixed = false;
-    uint64_t first = n, m64 = 0;
-    if (n == 0 || (n == 1 && ld_char(rq, 0, cs) == (uint32_t)'*')) {
-        fixed = kSimWildcard;
-        is_fixed = true;
-    } else {
-        for (uint64_t base = 0; base < n; base += 64) {
-            const uint64_t i = base + lane;
-            const uint64_t bal = __ballot(i < n && sim_keeps(s_valid, ld_char(rq, i, cs), cs));
-            if (bal) {
-                first = base + (uint32_t)__ffsll((unsigned long long)bal) - 1u;
-                break;
-            }
-        }
-        if (first < n) {
-            uint64_t last = first;
-            for (uint64_t base = 0; base < n; base += 64) {
-                const uint64_t i = base + lane;
-                const uint64_t bal = __ballot(i < n && sim_keeps(s_valid, ld_char(rq, n - 1 - i, cs), cs));
-                if (bal) {
-                    last = n - 1 - (base + (uint32_t)__ffsll((unsigned long long)bal) - 1u);
-                    break;
-                }
-            }
-            m64 = last - first + 1;
-        }
-        if (m64 > kSimMaxQuery) {
-            fixed = kSimNone;
-            is_fixed = true;
-        }
-    }
-    if (is_fixed) {
-        for (uint32_t r = lane; r < count; r += 64) {
-            out[r] = fixed;
-            if constexpr (kTerms) out_t[r] = kSimNoTerm;
-        }
-        return;
-    }
-    const uint32_t m = (uint32_t)m64;
-    const uint8_t* nq = rq + first * cs;
-
-    if (m <= 64) {
-        // ---- short path: lanes are records, each in the member of its key ----
-        const uint32_t qc = lane < m ? sim_norm(s_valid, ld_char(nq, lane, cs), cs) : kSimEmpty;
-        uint64_t mine = 0;
-        for (uint32_t i = 0; i < m; ++i) mine |= __shfl(qc, (int)i) == qc ? 1ull << i : 0ull;
-        if (kWide) {
-            s_key[lane] = kSimEmpty;
-            s_key[lane + 64] = kSimEmpty;
-        } else {
-            for (uint32_t i = lane; i < 256; i += 64) s_mask[i] = 0;
-        }
-        __syncthreads();
-        if (lane < m) {
-            if (!kWide) {
-                s_mask[qc] = mine;
-            } else if ((uint32_t)__ffsll((unsigned long long)mine) - 1u == lane) {
-                uint32_t s = sim_slot(qc);
-                for (;;) {
-                    const uint32_t old = atomicCAS(&s_key[s], kSimEmpty, qc);
-                    if (old == kSimEmpty || old == qc) break;
-                    s = (s + 1u) & (kSimSlots - 1u);
-                }
-                s_mask[s] = mine;
-            }
-        }
-        __syncthreads();
-
-        // a record's place in its member: the member p, the local key, the terms [j, je) still to
-        // compare and the first of them, tt = [ta, tb). A global id at or past `total` has none.
+        // a record's place in its index: the member p, the local key, the terms [j, je) still to
+        // compare and the first of them, tt = [ta, tb) (tt is read with kTerms). A key id at or past
+        // src.total has none, and nothing is read through it.
         struct Rec {
             uint32_t p, key, j, je, tt;
             uint64_t ta, tb;
         };
         auto first_term = [&](uint32_t g) {
-            Rec f{0, 0, 0, 0, kSimNoTerm, 0, 0};
-            if (g >= total) return f;
-            f.p = set_member(s_m, P, g);
-            const SimMember& M = s_m[f.p];
+            Rec f{0, g, 0, 0, kSimNoTerm, 0, 0};  // (the key starts as the id: see the long path)
+            if (g >= src.total) return f;
+            f.p = src.member(g);
+            const SimMember& M = src.at(f.p);
             f.key = g - M.base;
             if (f.key >= M.n_keys) return f;
             key_terms(M, f.key, f.j, f.je);
@@ -508,13 +290,13 @@ __global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32
         for (uint32_t base = 0; base < count; base += 64) {
             const uint32_t r = base + lane, rn = r + 64;
             const Rec nx = first_term(rn < count ? keys[rn] : kSimEmpty);
-            const SimMember& M = s_m[c.p];
+            const SimMember& M = src.at(c.p);
             float best = kSimNone;
             uint32_t best_t = kSimNoTerm;
             while (c.j < c.je) {
                 if (c.tb > c.ta) {
                     const uint32_t L = (uint32_t)(c.tb - c.ta);
-                    uint32_t d = kMetric == kSimPartial ? 0u : L;
+                    uint32_t d = kMetric == kSimPartial ? 0u : L;  // an empty Q: L insertions (partial: none)
                     if (m) {
                         if (kWide)
                             d = myers_wide<kMetric>(s_mask, s_key, m, reinterpret_cast<const uint32_t*>(M.term_bytes) + c.ta, L);
@@ -541,11 +323,12 @@ __global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32
         return;
     }
 
-    // ---- long path: the systolic pipeline, one record at a time; its member is uniform over the wave ----
+    // ---- long path: the wave is a systolic pipeline over the query's W words ----
     const uint32_t W = (m + 63u) / 64u;
     const uint32_t rows = lane + 1u < W ? 64u : (lane < W ? m - 64u * lane : 0u);
     const uint64_t top = rows ? 1ull << (rows - 1u) : 0ull;
     const uint64_t rowmask = rows == 64u ? ~0ull : (1ull << rows) - 1ull;
+    // this lane's 64 query characters: bytes packed four to a register, or one register each
     constexpr uint32_t kRegs = kWide ? 64u : 16u;
     uint32_t qw[kRegs];
 #pragma unroll
@@ -556,13 +339,16 @@ __global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32
         if (kWide) qw[i] = c;
         else qw[i >> 2] |= c << (8u * (i & 3u));
     }
-    for (uint32_t r = 0; r < count; ++r) {
+    for (uint32_t r = 0; r < count; ++r) {  // (the record's member is uniform over the wave)
         const uint32_t g = keys[r];
         float best = kSimNone;
         uint32_t best_t = kSimNoTerm;
-        uint32_t j = 0, je = 0, key = 0;
-        const SimMember& M = s_m[g < total ? set_member(s_m, P, g) : 0u];
-        if (g < total) {
+        // The local key starts as the id, not as 0: a key outside the source is never read, and for one
+        // index (base 0) the id is then used as loaded. Started at 0 it is a select that cost the
+        // single-index kernels with terms up to 9 VGPRs and one of them a wave (profiles/sim_one_body_isa.txt).
+        uint32_t j = 0, je = 0, key = g;
+        const SimMember& M = src.at(g < src.total ? src.member(g) : 0u);
+        if (g < src.total) {
             key = g - M.base;
             if (key < M.n_keys) key_terms(M, key, j, je);
         }
@@ -573,10 +359,11 @@ __global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32
             const uint32_t L = (uint32_t)(M.term_off[t + 1] - ta);
             if (!L) continue;
             SimBlock<kMetric> b;
-            uint32_t score = m, low = m;
-            int hout = 0;
+            uint32_t score = m, low = m;  // followed by lane W - 1
+            int hout = 0;  // kSimOsa: the transposition bit rides in bit 2 of hout + 1
             const uint32_t steps = L + W - 1u;
             for (uint32_t s = 0; s < steps; ++s) {
+                // lane w is at term character s - w, with the delta lane w - 1 left at it one step ago
                 const int up = __shfl_up(hout, 1);
                 int hin = lane == 0 ? kSimTopDelta<kMetric> : up;
                 uint32_t tin = 0, tout = 0;
@@ -585,7 +372,7 @@ __global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32
                     hin = lane == 0 ? +1 : (int)((uint32_t)up & 3u) - 1;
                 }
                 const uint32_t at = s - lane;
-                if (lane < W && at < L) {
+                if (lane < W && at < L) {  // (s < lane wraps past L)
                     const uint32_t c = ld_char(M.term_bytes, ta + at, cs);
                     uint64_t eq = 0;
 #pragma unroll
@@ -606,6 +393,26 @@ __global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32
             if constexpr (kTerms) out_t[r] = best_t;
         }
     }
+}
+
+// Two kernels, one per source: a single index keeps its registers and its waves,
+// a set pays for the member table. One wave per query, both.
+template <bool kWide, uint32_t kMetric, bool kTerms>
+__global__ __launch_bounds__(64) void k_sim(DevIndex X, SimArgs A) {
+    const OneIndex one{{X.kt_off, X.kt_term, A.key_term, X.term_off, X.term_bytes, X.n_keys, X.n_terms, 0u, 0u}, X.n_keys};
+    sim_wave<kWide, kMetric, kTerms>(one, A);
+}
+// The descriptors travel by value in the kernel arguments and are copied to LDS once; the members
+// tile [0, total) in order (launch_similarity_set checks it).
+template <bool kWide, uint32_t kMetric, bool kTerms>
+__global__ __launch_bounds__(64) void k_sim_set(SimMembers T, uint32_t P, uint32_t total, SimArgs A) {
+    __shared__ SimMember s_m[kSetMaxParts];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (uint32_t p = 0; p < kSetMaxParts; ++p)
+            if (p < P) s_m[p] = T.m[p];  // (constant indexes: scalar loads; entries from P on are never read)
+    }
+    sim_wave<kWide, kMetric, kTerms>(IndexSet{s_m, P, total}, A);
 }
 
 // ---- re-rank ----
@@ -752,15 +559,30 @@ __global__ __launch_bounds__(256) void k_key_term(DevIndex X, uint32_t* __restri
 }  // namespace
 
 namespace {
-template <uint32_t kMetric, bool kTerms>
-void launch_sim_as(const DevIndex& X, const SimArgs& A, hipStream_t s) {
-    if (X.csize == 4) hipLaunchKernelGGL((k_sim<true, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, X, A);
-    else hipLaunchKernelGGL((k_sim<false, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, X, A);
+// The instantiation of (metric, terms, width) for either kernel: K names the kernel's family, `lead`
+// are the arguments it takes in front of A. One wave per query.
+struct OneIndexKernel {
+    template <bool kWide, uint32_t kMetric, bool kTerms>
+    static constexpr auto kernel = &k_sim<kWide, kMetric, kTerms>;
+};
+struct IndexSetKernel {
+    template <bool kWide, uint32_t kMetric, bool kTerms>
+    static constexpr auto kernel = &k_sim_set<kWide, kMetric, kTerms>;
+};
+template <class K, uint32_t kMetric, class... Lead>
+void launch_sim_as(uint32_t cs, const SimArgs& A, hipStream_t s, const Lead&... lead) {
+    auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(A.n), dim3(64), 0, s, lead..., A); };
+    if (A.terms) go(cs == 4 ? K::template kernel<true, kMetric, true> : K::template kernel<false, kMetric, true>);
+    else go(cs == 4 ? K::template kernel<true, kMetric, false> : K::template kernel<false, kMetric, false>);
 }
-template <uint32_t kMetric>
-void launch_sim_by_terms(const DevIndex& X, const SimArgs& A, hipStream_t s) {
-    if (A.terms) launch_sim_as<kMetric, true>(X, A, s);
-    else launch_sim_as<kMetric, false>(X, A, s);
+template <class K, class... Lead>
+hipError_t launch_sim(uint32_t metric, uint32_t cs, const uint32_t valid[8], SimArgs A, hipStream_t s,
+                      const Lead&... lead) {
+    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
+    if (metric == kSimOsa) launch_sim_as<K, kSimOsa>(cs, A, s, lead...);
+    else if (metric == kSimPartial) launch_sim_as<K, kSimPartial>(cs, A, s, lead...);
+    else launch_sim_as<K, kSimLevenshtein>(cs, A, s, lead...);
+    return hipGetLastError();
 }
 }  // namespace
 
@@ -770,27 +592,9 @@ hipError_t launch_similarity(const DevIndex& X, const uint32_t valid[8], const u
     if (metric >= kSimMetrics) return hipErrorInvalidValue;
     if (!n || !stride) return hipSuccess;
     if (!X.kt_off && !key_term) return hipErrorInvalidValue;
-    SimArgs A{raw, off, counts, keys, sim, terms, key_term, n, stride, {}};
-    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
-    if (metric == kSimOsa) launch_sim_by_terms<kSimOsa>(X, A, s);
-    else if (metric == kSimPartial) launch_sim_by_terms<kSimPartial>(X, A, s);
-    else launch_sim_by_terms<kSimLevenshtein>(X, A, s);
-    return hipGetLastError();
+    return launch_sim<OneIndexKernel>(metric, X.csize, valid, {raw, off, counts, keys, sim, terms, key_term, n, stride, {}},
+                                      s, X);
 }
-
-namespace {
-template <uint32_t kMetric, bool kTerms>
-void launch_sim_set_as(const SimMembers& T, uint32_t P, uint32_t total, uint32_t cs, const SimArgs& A, hipStream_t s) {
-    if (cs == 4) hipLaunchKernelGGL((k_sim_set<true, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, T, P, total, A);
-    else hipLaunchKernelGGL((k_sim_set<false, kMetric, kTerms>), dim3(A.n), dim3(64), 0, s, T, P, total, A);
-}
-template <uint32_t kMetric>
-void launch_sim_set_by_terms(const SimMembers& T, uint32_t P, uint32_t total, uint32_t cs, const SimArgs& A,
-                             hipStream_t s) {
-    if (A.terms) launch_sim_set_as<kMetric, true>(T, P, total, cs, A, s);
-    else launch_sim_set_as<kMetric, false>(T, P, total, cs, A, s);
-}
-}  // namespace
 
 hipError_t launch_similarity_set(const SimMembers& T, uint32_t P, uint32_t cs, const uint32_t valid[8],
                                  const uint8_t* raw, const uint64_t* off, uint32_t n, uint32_t stride,
@@ -805,12 +609,8 @@ hipError_t launch_similarity_set(const SimMembers& T, uint32_t P, uint32_t cs, c
         total += M.n_keys;
     }
     if (total > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    SimArgs A{raw, off, counts, keys, sim, terms, nullptr, n, stride, {}};
-    for (int i = 0; i < 8; ++i) A.V.w[i] = valid[i];
-    if (metric == kSimOsa) launch_sim_set_by_terms<kSimOsa>(T, P, (uint32_t)total, cs, A, s);
-    else if (metric == kSimPartial) launch_sim_set_by_terms<kSimPartial>(T, P, (uint32_t)total, cs, A, s);
-    else launch_sim_set_by_terms<kSimLevenshtein>(T, P, (uint32_t)total, cs, A, s);
-    return hipGetLastError();
+    return launch_sim<IndexSetKernel>(metric, cs, valid, {raw, off, counts, keys, sim, terms, nullptr, n, stride, {}}, s, T,
+                                      P, (uint32_t)total);
 }
 
 hipError_t launch_rerank(uint32_t n, uint32_t stride, uint32_t* counts, uint32_t* keys, float* scores, float* sim,

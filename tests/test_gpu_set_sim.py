@@ -211,6 +211,39 @@ def test_planted_records_equal_the_per_member_model(planted, P):
         view.set.dispose()
 
 
+@pytest.mark.parametrize("p", [0, 1], ids=["several_terms", "one_pair"])
+def test_a_member_alone_equals_the_model_on_both_paths(planted, p):
+    """ngsSimilarityDeviceM on one member's handle, the body the set runs with the index in registers: keys
+    that list their terms (kt_off) and keys with one pair (the key_term map), query lengths at the path
+    cut-over (64 | 65) and one past two words, row counts at the round boundary of the short path, and
+    ids at and past nKeys, which read nothing."""
+    member = planted.members[p]
+    cs = 4 if planted.wide else 1
+    rng = random.Random(0x94 + p)
+    queries, cn, keys = [], [], []
+    for m in (1, 64, 65, 129):
+        mine = [k for q, k in planted.planted[m] if q == p]
+        for c in (1, 64, 65):
+            row = mine + [rng.randrange(member.nk) for _ in range(c)]
+            queries.append(planted.raw(m))
+            cn.append(c)
+            keys.append(row[:c])
+        queries.append(planted.raw(m))
+        edge = [0, member.nk, 0xFFFFFFFF, member.nk - 1]
+        cn.append(len(edge))
+        keys.append(edge)
+    assert any(len(member.key_terms[k]) > 1 for row in keys for k in row if k < member.nk) == (p == 0)
+    for metric in METRICS:
+        want, want_t = mc.expect_m(queries, cn, keys, 65, member.key_terms, member.term_ids, metric, wide=planted.wide)
+        got, got_t = mc.similarity_m(member.ix, queries, cn, keys, 65, metric, True, cs)
+        mc.check_cells(got, want, f"member {p} metric {metric} sims")
+        mc.check_cells(got_t, want_t, f"member {p} metric {metric} terms")
+        alone, none = mc.similarity_m(member.ix, queries, cn, keys, 65, metric, False, cs)
+        assert none is None
+        mc.check_cells(alone, want, f"member {p} metric {metric} sims without dTerms")
+        assert want_t[3][1] == want_t[3][2] == NO_TERM != want_t[3][0]
+
+
 # ---- NGS_SIM_TOKEN_SORT ---------------------------------------------------------------------------------
 def test_token_sort_route_first_flagged_call_included():
     rng = random.Random(0x93)

@@ -42,7 +42,7 @@ def test_header_declares_and_library_exports_the_symbols():
         assert callable(getattr(ssl.IndexSet, m)), m
     assert ssl.METRICS == {"levenshtein": 0, "osa": 1, "partial": 2}
     # the members' table travels in the kernel arguments: 16 x 56 bytes
-    text = open(os.path.join(ROOT, "stringsearchlib_amd", "csrc", "ngs_set.h")).read()
+    text = open(os.path.join(ROOT, "stringsearchlib_amd", "csrc", "ngs_sim.h")).read()
     assert re.search(r"static_assert\(sizeof\(SimMember\) == 56", text)
 
 

@@ -30,7 +30,7 @@ for (mangled, r), dn in zip(rows.items(), names):
         continue
     dn = dn.replace("ngs::(anonymous namespace)::", "").replace("ngs::", "")
     dn = re.sub(r"\(.*", "", dn.replace("void ", "", 1))
-    print(f"{dn[:64]:64s} VGPR {r.get('VGPRs', '?'):>4} AGPR {r.get('AGPRs', '?'):>3} scratch {r.get('ScratchSize [bytes/lane]', '?'):>4} "
+    print(f"{dn[:64]:64s} VGPR {r.get('VGPRs', '?'):>4} AGPR {r.get('AGPRs', '?'):>3} SGPR {r.get('TotalSGPRs', '?'):>3} scratch {r.get('ScratchSize [bytes/lane]', '?'):>4} "
           f"occ {r.get('Occupancy [waves/SIMD]', '?'):>2} vspill {r.get('VGPRs Spill', '?'):>3} sspill {r.get('SGPRs Spill', '?'):>3} "
           f"lds {r.get('LDS Size [bytes/block]', '?')}")
 if res.returncode:
