@@ -689,6 +689,69 @@ NGS_API uint32_t scoreBatchSetW(uint32_t set, const wchar_t* const* queries, uin
 NGS_API uint32_t scoreBatchSetU8(uint32_t set, const char* const* queries, uint32_t nQueries, float threshold,
                                  uint32_t limit, uint32_t stride, uint32_t* counts, uint32_t* keyIds, float* scores);
 
+/* ---- Dead keys: delete from a set without a rebuild ----
+ * Definition. A set keeps, per member, a dead mask of one bit per local key id, on its device as it
+ * keeps the length tables. Every answer of a set with dead keys is the answer of a set over the same
+ * members with the rows of the dead master keys left out, compared by key string, order and fp32 score
+ * bits. The global key ids are the unchanged ones of the full set (base_p + k): ids are stable under
+ * delete as they are under append. To update a key, remove it and append the new row.
+ *
+ * Exactness. A key's score depends on its own row only and the whole library's order is (score
+ * descending, length ascending, part ascending, local id ascending): removing records from a totally
+ * ordered list keeps the order of the rest. The dead records are dropped before a row is cut to the
+ * limit, never after it.
+ *
+ * The members are never changed: a handle searched directly still answers with all its keys, and a
+ * handle in two sets has two independent masks. ngsSetNumKeys, ngsSetLocate, ngsKey*,
+ * ngsSetKeyQueriesDevice and ngsSetSimilarityDeviceM are unchanged too: a dead key keeps its id and its
+ * string, and a record a caller hands in is measured whether its key is dead or not.
+ *
+ * Searches. A member without dead keys is searched as before, and a set without dead keys launches
+ * exactly what it launched before. A member with d dead keys is searched at limit L + E into a block of
+ * stride min(L + E, nKeys_p) (the sum in 64 bits; at or above 2^31-1 means all); one ngsDropDeadDevice
+ * launch over all such members cuts every row to L, then the merge follows. E starts at min(d, E0),
+ * E0 = 128 - L for L <= 112 (the search's fastest tier takes limits up to 128) and max(L, 64) above;
+ * the members' short-row counters are read back once (the one extra wait a set with dead keys takes),
+ * and a member with short rows whose stride was below both L + d and nKeys_p is searched again with E
+ * four times as large, capped at d, where the answer is exact.
+ *
+ * Self-join and clusters. A dead key is never a hit. The row of a dead query key is empty
+ * (ngsSetSelfJoinDevice, selfJoinSet: count 0); dedupKeysSet gives labels[g] = g for a dead g and
+ * returns the number of clusters of the live keys.
+ *
+ * ngsDropDeadDevice: the row rule on a block in ngsSearchDevice's layout, in place. Per row i < n, with
+ * c = min(dCounts[i], stride): every record whose key k < nKeys has bit k & 31 of dDead[k >> 5] set is
+ * removed (a k >= nKeys is live, nothing is read through it); the remaining records keep their order
+ * and move up; the row is cut to L = limit ? limit : 2^31-1; dCounts[i] is the new count. Cells past
+ * the new count are unspecified; nothing at or beyond i * stride + stride is written. If dShort is not
+ * NULL, *dShort is increased by the number of short rows: rows with c == stride and fewer than L
+ * records left, for which the search may have had more hits behind the block. It takes no handle, like
+ * ngsDropSelfDevice; one kernel, no atomics on the records, reproducible bit for bit; queued on
+ * `stream`, nothing waits. 0 ok (n = 0 included); -3 NULL dCounts, NULL dKeys or dScores with n and
+ * stride non-zero, NULL dDead with nKeys > 0, n above 2^31-1; -4 HIP error.
+ *
+ * ngsSetRemove: the global ids keyIds[n] (a host array) become dead; duplicates and ids already dead
+ * are fine. Returns the number of keys newly dead. -3 for an id >= ngsSetNumKeys or NULL keyIds with
+ * n > 0, with nothing changed (every id is checked first); -1 unknown set or a disposed member; -4 HIP
+ * error. It excludes every other call on the library while it runs, like ngsSetAdd, so a search sees
+ * all or none of a call's changes, and the masks on the device are up to date when it returns.
+ * ngsSetRestore: the same with the bits cleared; returns the number newly live.
+ * ngsSetLiveKeys: the number of live keys (0 for an unknown set). ngsSetDeadKeys: the number of dead
+ * keys, their first `cap` global ids written to out ascending (out may be NULL with cap 0): what a
+ * caller stores to persist a set's deletions. ngsSetIsLive: 1 or 0; -1; -3 for an id past the set.
+ * ngsSetDeadStats: out[0 .. min(n, NGS_SET_DEAD_STATS)) = counters since the set was made: the
+ * ngsDropDeadDevice launches of its searches, the member re-searches, the largest over-fetch E used.
+ * Returns NGS_SET_DEAD_STATS; -1; -3 n < 0 or NULL out with n > 0. */
+#define NGS_SET_DEAD_STATS 3u
+NGS_API int ngsDropDeadDevice(uint32_t* dCounts, uint32_t* dKeys, float* dScores, uint32_t n, uint32_t stride,
+                              const uint32_t* dDead, uint32_t nKeys, uint32_t limit, uint32_t* dShort, void* stream);
+NGS_API int ngsSetRemove(uint32_t set, const uint32_t* keyIds, uint32_t n);
+NGS_API int ngsSetRestore(uint32_t set, const uint32_t* keyIds, uint32_t n);
+NGS_API uint32_t ngsSetLiveKeys(uint32_t set);
+NGS_API uint32_t ngsSetDeadKeys(uint32_t set, uint32_t* out, uint32_t cap);
+NGS_API int ngsSetIsLive(uint32_t set, uint32_t keyId);
+NGS_API int ngsSetDeadStats(uint32_t set, uint64_t* out, int n);
+
 /* ---- The later stages over a set ----
  * Key ids are the set's global ones everywhere below. Member p owns g iff base_p <= g < base_p +
  * nKeys_p. Every answer is the one a single index over all the members' rows would give (no master

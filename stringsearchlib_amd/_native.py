@@ -185,6 +185,14 @@ EXPORTS = [
             "scoreBatchSetSimM": (u32, [u32, STRS, u32, f32, u32, u32, f32, u32, PU, PU, P(f32), P(f32), PU])}),
         "selfJoinSet": (u32, [u32, u32, u32, f32, u32, u32, PU, PU, P(f32)]),
         "dedupKeysSet": (u32, [u32, f32, u32, u32, f32, u32, PU])}),
+    # dead keys: delete from a set without a rebuild
+    ("ngsDropDeadDevice", {"ngsDropDeadDevice": (ci, [vp, vp, vp, u32, u32, vp, u32, u32, vp, vp]),
+                           "ngsSetRemove": (ci, [u32, PU, u32]),
+                           "ngsSetRestore": (ci, [u32, PU, u32]),
+                           "ngsSetLiveKeys": (u32, [u32]),
+                           "ngsSetDeadKeys": (u32, [u32, PU, u32]),
+                           "ngsSetIsLive": (ci, [u32, u32]),
+                           "ngsSetDeadStats": (ci, [u32, P(u64), ci])}),
     ("ngsServeState", {"ngsServeState": (ci, [u32])}),
     ("ngsLastError", {"ngsLastError": (ci, [ci])}),
     ("ngsReplicaDigest", {"ngsReplicaDigest": (ci, [u32, ci, P(u64), ci])}),

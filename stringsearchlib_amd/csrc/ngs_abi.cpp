@@ -3059,14 +3059,23 @@ struct KeySet {
         uint64_t serial = 0;
         uint32_t base = 0, n_keys = 0;
         uint32_t* d_len = nullptr;  // [n_keys] on `device`
+        // the dead mask (§9.9), one bit a key: made by the member's first ngsSetRemove, the device's
+        // copy equal to the host's whenever the exclusive lock is released
+        std::vector<uint32_t> dead;
+        uint32_t* d_dead = nullptr;
+        uint32_t n_dead = 0;
     };
     std::vector<Member> parts;
     int device = 0;
     uint32_t csize = 0, gsz = 0;
-    uint64_t n_keys = 0;
+    uint64_t n_keys = 0, n_dead = 0;
+    // ngsSetDeadStats: searches count under the shared lock
+    mutable std::atomic<uint64_t> drop_launches{0}, re_searches{0}, max_fetch{0};
     ~KeySet() {
-        for (Member& m : parts)
+        for (Member& m : parts) {
             if (m.d_len) (void)hipFree(m.d_len);
+            if (m.d_dead) (void)hipFree(m.d_dead);
+        }
     }
 };
 std::unordered_map<uint32_t, std::unique_ptr<KeySet>> g_sets;  // a namespace of its own (under g_lock)
@@ -3126,25 +3135,62 @@ uint32_t set_effective_limit(const KeySet& S, uint32_t limit) {
 }
 
 // The members' blocks of a set search of up to `rows` queries at `limit`, in M: member p's has the
-// stride min(L, nKeys_p).
+// stride min(L, nKeys_p); a member with dead keys (§9.9) the stride of its first over-fetch (0 when
+// all its keys are dead), and the set then has the members' short-row counters too (a set without
+// dead keys allocates what it did before).
 struct SetBlocks {
     MergeParts parts{};
     uint64_t records = 0;  // per query, all members
+    size_t rows = 0;
+    uint32_t cap[kSetMaxParts] = {};  // the records a row of member p's block has room for
+    uint32_t* d_short = nullptr;      // [kSetMaxParts]
 };
+// the stride member p's block starts with: min(L, nKeys_p), or that of its first over-fetch
+uint32_t set_first_stride(const KeySet& S, Library* const* libs, size_t p, uint32_t limit) {
+    const uint32_t d = S.parts[p].n_dead, L = set_limit(limit);
+    if (d && d == S.parts[p].n_keys) return 0;  // wholly dead: never searched, no records
+    return d ? dead_fetch_stride(L, dead_first_fetch(d, L), S.parts[p].n_keys) : effective_limit(*libs[p], limit);
+}
 bool set_blocks(CallScratch& M, const KeySet& S, Library* const* libs, size_t rows, uint32_t limit, SetBlocks& K) {
+    K.rows = rows;
     for (size_t p = 0; p < S.parts.size(); ++p) {
         MergePart& B = K.parts.p[p];
-        B.stride = effective_limit(*libs[p], limit);
+        B.stride = set_first_stride(S, libs, p, limit);
         B.base = S.parts[p].base;
         B.n_keys = S.parts[p].n_keys;
         B.len = S.parts[p].d_len;
-        uint32_t *d_n = nullptr, *d_k = nullptr;
-        float* d_s = nullptr;
-        if (!M.alloc(&d_n, rows) || !M.alloc(&d_k, rows * B.stride) || !M.alloc(&d_s, rows * B.stride)) return false;
-        B.counts = d_n;
-        B.keys = d_k;
-        B.scores = d_s;
+        K.cap[p] = B.stride;
         K.records += B.stride;
+    }
+    if (!S.n_dead) {  // (as before dead keys existed: three allocations a member)
+        for (size_t p = 0; p < S.parts.size(); ++p) {
+            MergePart& B = K.parts.p[p];
+            uint32_t *d_n = nullptr, *d_k = nullptr;
+            float* d_s = nullptr;
+            if (!M.alloc(&d_n, rows) || !M.alloc(&d_k, rows * B.stride) || !M.alloc(&d_s, rows * B.stride)) return false;
+            B.counts = d_n;
+            B.keys = d_k;
+            B.scores = d_s;
+        }
+        return true;
+    }
+    // With dead keys the blocks are wider, and an allocation of 2 MiB and more was measured at some
+    // 0.18 ms each (§9.9): all blocks and the short counters are cut from one allocation, every
+    // array starting at a multiple of 256 bytes.
+    auto pad = [](size_t words) { return (words + 63u) & ~size_t(63); };
+    size_t words = pad(kSetMaxParts);
+    for (size_t p = 0; p < S.parts.size(); ++p) words += pad(rows) + 2 * pad(rows * K.parts.p[p].stride);
+    uint32_t* slab = nullptr;
+    if (!M.alloc(&slab, words)) return false;
+    K.d_short = slab;
+    slab += pad(kSetMaxParts);
+    for (size_t p = 0; p < S.parts.size(); ++p) {
+        MergePart& B = K.parts.p[p];
+        const size_t recs = pad(rows * B.stride);
+        B.counts = slab;
+        B.keys = slab + pad(rows);
+        B.scores = reinterpret_cast<float*>(slab + pad(rows) + recs);
+        slab += pad(rows) + 2 * recs;
     }
     return true;
 }
@@ -3162,19 +3208,152 @@ struct SetGuards {
 // ngsSetSearchDevice's work (the shared lock and the members' SetGuards held, the set's device
 // current): every member searched into its block, one after another, then the merge queued on s.
 // Nothing waits for the merge.
-int set_search(const KeySet& S, Library* const* libs, const SetBlocks& K, const uint8_t* d_raw, const uint64_t* d_off,
-               uint32_t n, float thr, uint32_t limit, uint32_t out_stride, uint32_t* d_n, uint32_t* d_k, float* d_s,
-               hipStream_t s) {
-    for (size_t p = 0; p < S.parts.size(); ++p) {
+// With dead keys (§9.9) a member that has some is searched at L + E_p into a block of stride
+// min(L + E_p, nKeys_p), and one k_drop_dead launch over those members cuts their rows to L before
+// the merge. The members' short-row counters are read back once a round (the one extra wait, taken
+// only when the set has dead keys): a member with short rows whose stride was below both L + d_p and
+// nKeys_p is searched again with a larger E_p, into a larger block from M where it needs one.
+int set_search(const KeySet& S, Library* const* libs, CallScratch& M, SetBlocks& K, const uint8_t* d_raw,
+               const uint64_t* d_off, uint32_t n, float thr, uint32_t limit, uint32_t out_stride, uint32_t* d_n,
+               uint32_t* d_k, float* d_s, hipStream_t s) {
+    const uint32_t P = (uint32_t)S.parts.size(), L = set_limit(limit);
+    auto search = [&](uint32_t p) {
         Replica* R = libs[p]->replica_at(S.device);
         if (!R) return -3;
         const MergePart& B = K.parts.p[p];
-        if (const int rc = search_on_replica(*libs[p], *R, d_raw, d_off, n, thr, B.stride, B.stride,
-                                             const_cast<uint32_t*>(B.counts), const_cast<uint32_t*>(B.keys),
-                                             const_cast<float*>(B.scores), s))
-            return rc;
+        return search_on_replica(*libs[p], *R, d_raw, d_off, n, thr, B.stride, B.stride, const_cast<uint32_t*>(B.counts),
+                                 const_cast<uint32_t*>(B.keys), const_cast<float*>(B.scores), s);
+    };
+    auto fetched = [&](uint32_t E) {  // ngsSetDeadStats: the largest over-fetch used
+        uint64_t seen = S.max_fetch.load(std::memory_order_relaxed);
+        while (seen < E && !S.max_fetch.compare_exchange_weak(seen, E, std::memory_order_relaxed)) {
+        }
+    };
+    uint32_t E[kSetMaxParts] = {}, todo = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+        const uint32_t d = S.parts[p].n_dead;
+        if (d && d == S.parts[p].n_keys) {  // wholly dead: it can give no record, so it is not searched
+            if (!HIP_CHECK(hipMemsetAsync(const_cast<uint32_t*>(K.parts.p[p].counts), 0, sizeof(uint32_t) * n, s))) return -4;
+            continue;
+        }
+        if (d) {
+            E[p] = dead_first_fetch(d, L);
+            K.parts.p[p].stride = dead_fetch_stride(L, E[p], S.parts[p].n_keys);  // (<= K.cap[p]: set_blocks)
+            fetched(E[p]);
+            todo |= 1u << p;
+        }
+        if (const int rc = search(p)) return rc;
     }
-    return HIP_CHECK(launch_merge_parts(K.parts, (uint32_t)S.parts.size(), n, limit, out_stride, d_n, d_k, d_s, s)) ? 0 : -4;
+    while (todo) {
+        DropBlocks D{};
+        uint32_t nb = 0, h_short[kSetMaxParts] = {};
+        for (uint32_t p = 0; p < P; ++p) {
+            if (!(todo >> p & 1u)) continue;
+            const MergePart& B = K.parts.p[p];
+            D.b[nb++] = DropBlock{const_cast<uint32_t*>(B.counts), const_cast<uint32_t*>(B.keys),
+                                  const_cast<float*>(B.scores), S.parts[p].d_dead, K.d_short + p, B.stride, B.n_keys};
+        }
+        if (!HIP_CHECK(hipMemsetAsync(K.d_short, 0, sizeof h_short, s)) || !HIP_CHECK(launch_drop_dead(D, nb, n, limit, s)) ||
+            !HIP_CHECK(hipMemcpyAsync(h_short, K.d_short, sizeof h_short, hipMemcpyDeviceToHost, s)) ||
+            !HIP_CHECK(hipStreamSynchronize(s)))
+            return -4;
+        S.drop_launches.fetch_add(1, std::memory_order_relaxed);
+        uint32_t again = 0;
+        for (uint32_t p = 0; p < P; ++p) {
+            if (!(todo >> p & 1u)) continue;
+            MergePart& B = K.parts.p[p];
+            const uint32_t d = S.parts[p].n_dead;
+            if (!h_short[p] || B.stride >= dead_fetch_stride(L, d, B.n_keys)) continue;
+            E[p] = dead_next_fetch(d, E[p]);
+            B.stride = dead_fetch_stride(L, E[p], B.n_keys);
+            if (B.stride > K.cap[p]) {
+                uint32_t* keys = nullptr;
+                float* scores = nullptr;
+                if (!M.alloc(&keys, K.rows * B.stride) || !M.alloc(&scores, K.rows * B.stride)) return -4;
+                B.keys = keys;
+                B.scores = scores;
+                K.cap[p] = B.stride;
+            }
+            fetched(E[p]);
+            S.re_searches.fetch_add(1, std::memory_order_relaxed);
+            if (const int rc = search(p)) return rc;
+            again |= 1u << p;
+        }
+        todo = again;
+    }
+    return HIP_CHECK(launch_merge_parts(K.parts, P, n, limit, out_stride, d_n, d_k, d_s, s)) ? 0 : -4;
+}
+
+static_assert(kSetDeadFastLimit == kWaveMaxLimit, "the first over-fetch fills tier 1's limit");
+
+// The rows of a join over keys [first, first + n) whose own key is dead emptied (§9.9), queued on s;
+// nothing is launched for a set without dead keys.
+bool set_zero_dead_rows(const KeySet& S, uint32_t* d_n, uint32_t n, uint32_t first, hipStream_t s) {
+    if (!S.n_dead) return true;
+    DeadMasks D{};
+    for (size_t p = 0; p < S.parts.size(); ++p) {
+        D.dead[p] = S.parts[p].n_dead ? S.parts[p].d_dead : nullptr;
+        D.base[p] = S.parts[p].base;
+        D.n_keys[p] = S.parts[p].n_keys;
+    }
+    return HIP_CHECK(launch_zero_dead_rows(D, (uint32_t)S.parts.size(), d_n, n, first, s));
+}
+
+// ngsSetRemove (dead = true) / ngsSetRestore under the exclusive lock: every id checked before
+// anything changes, the bits flipped in copies of the touched members' masks, the copies uploaded,
+// and only then kept. No search is in flight (each holds the shared lock until its results are
+// complete), so the device's masks change between two searches.
+int set_mark(uint32_t set, const uint32_t* ids, uint32_t n, bool dead) {
+    std::unique_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (n && !ids) return -3;
+    for (uint32_t i = 0; i < n; ++i)
+        if (ids[i] >= S->n_keys) return -3;
+    const size_t P = S->parts.size();
+    std::vector<std::vector<uint32_t>> next(P);
+    std::vector<uint32_t> changed(P, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        size_t p = P - 1;  // (as ngsSetLocate)
+        while (S->parts[p].base > ids[i]) --p;
+        KeySet::Member& m = S->parts[p];
+        if (next[p].empty()) {
+            next[p] = m.dead;
+            next[p].resize(((size_t)m.n_keys + 31u) / 32u, 0u);
+        }
+        const uint32_t k = ids[i] - m.base, bit = 1u << (k & 31u);
+        if (((next[p][k >> 5] & bit) != 0u) == dead) continue;
+        next[p][k >> 5] ^= bit;
+        ++changed[p];
+    }
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    bool ok = HIP_CHECK(hipSetDevice(S->device));
+    size_t done = 0;
+    for (; ok && done < P; ++done) {
+        KeySet::Member& m = S->parts[done];
+        if (!changed[done]) continue;
+        ok = (m.d_dead || dev_alloc(&m.d_dead, next[done].size())) &&
+             HIP_CHECK(hipMemcpy(m.d_dead, next[done].data(), sizeof(uint32_t) * next[done].size(), hipMemcpyHostToDevice));
+    }
+    if (!ok)  // the masks already uploaded go back to what the host keeps
+        for (size_t p = 0; p < done; ++p)
+            if (changed[p] && S->parts[p].d_dead && !S->parts[p].dead.empty())
+                (void)hipMemcpy(S->parts[p].d_dead, S->parts[p].dead.data(), sizeof(uint32_t) * S->parts[p].dead.size(),
+                                hipMemcpyHostToDevice);
+    if (cur >= 0) (void)hipSetDevice(cur);
+    if (!ok) return -4;
+    uint32_t total = 0;
+    for (size_t p = 0; p < P; ++p) {
+        if (!changed[p]) continue;
+        KeySet::Member& m = S->parts[p];
+        m.dead.swap(next[p]);
+        m.n_dead = dead ? m.n_dead + changed[p] : m.n_dead - changed[p];
+        total += changed[p];
+    }
+    S->n_dead = dead ? S->n_dead + total : S->n_dead - total;
+    return (int)std::min<uint32_t>(total, kInt32Max);
 }
 
 // ---- the later stages over a set (ngsSetSimilarityDeviceM .. dedupKeysSet) ----
@@ -3248,13 +3427,14 @@ bool set_key_queries(const KeySet& S, Library* const* libs, uint32_t first, uint
 
 // join_batch over a set (its device current, the lock and the members' guards held): the gather, the
 // set search with one record more, the key's own record dropped by its global id.
-int set_join_batch(const KeySet& S, Library* const* libs, const SetBlocks& K, uint32_t first, uint32_t n, float thr,
+int set_join_batch(const KeySet& S, Library* const* libs, CallScratch& M, SetBlocks& K, uint32_t first, uint32_t n, float thr,
                    uint32_t limit, uint32_t stride, uint8_t* d_raw, uint64_t* d_off, uint32_t* d_n, uint32_t* d_k,
                    float* d_s, hipStream_t s, bool wait) {
     if (!set_key_queries(S, libs, first, n, d_raw, d_off, s)) return -4;
-    if (const int rc = set_search(S, libs, K, d_raw, d_off, n, thr, set_join_limit(S, limit), stride, d_n, d_k, d_s, s))
+    if (const int rc = set_search(S, libs, M, K, d_raw, d_off, n, thr, set_join_limit(S, limit), stride, d_n, d_k, d_s, s))
         return rc;
-    if (!HIP_CHECK(launch_drop_self(d_n, d_k, d_s, n, stride, first, limit, s))) return -4;
+    if (!HIP_CHECK(launch_drop_self(d_n, d_k, d_s, n, stride, first, limit, s)) || !set_zero_dead_rows(S, d_n, n, first, s))
+        return -4;
     return !wait || HIP_CHECK(hipStreamSynchronize(s)) ? 0 : -4;
 }
 
@@ -3270,7 +3450,7 @@ struct SetJoin {
     }
     bool blocks(CallScratch& M, size_t rows, uint32_t limit) { return set_blocks(M, S, libs, rows, search_limit(limit), K); }
     int batch(CallScratch& M, uint32_t first, uint32_t n, float thr, uint32_t limit, uint32_t stride) {
-        return set_join_batch(S, libs, K, first, n, thr, limit, stride, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream,
+        return set_join_batch(S, libs, M, K, first, n, thr, limit, stride, M.d_raw, M.d_off, M.d_n, M.d_k, M.d_s, M.stream,
                               false);
     }
     int similarity(CallScratch& M, uint32_t n, uint32_t stride, float* d_v, uint32_t metric) {
@@ -3316,8 +3496,9 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
     if (!HIP_CHECK(hipSetDevice(S->device))) return fail(0);
     SetGuards guards(*S, libs);
     uint64_t per_query = 0;
-    for (size_t p = 0; p < S->parts.size(); ++p) per_query += effective_limit(*libs[p], limit);
-    const uint32_t chunk = (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1, kSimChunkRecords / per_query));
+    for (size_t p = 0; p < S->parts.size(); ++p) per_query += set_first_stride(*S, libs, p, limit);  // (the blocks' strides)
+    const uint32_t chunk =
+        (uint32_t)std::min<uint64_t>(nq, std::max<uint64_t>(1, kSimChunkRecords / std::max<uint64_t>(per_query, 1)));
     // every query's bytes as they go up (u8: the UTF-8 bytes), and the bytes of the largest chunk
     const uint32_t up = u8 ? 1u : cs;  // bytes per unit of what is uploaded
     QueryChunks Q(nq, chunk, [&](uint32_t i, size_t& bytes) -> const void* {
@@ -3346,7 +3527,7 @@ uint32_t set_batch(uint32_t set, const CharT* const* queries, uint32_t nq, float
             (u8 && !HIP_CHECK(launch_utf8_decode(d_u8, d_u8off, B, reinterpret_cast<uint32_t*>(M.d_raw), raw_cap,
                                                  M.d_off, d_u8temp, u8temp, M.stream))))
             return fail(0);
-        if (set_search(*S, libs, K, M.d_raw, M.d_off, B, thr, limit, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0)
+        if (set_search(*S, libs, M, K, M.d_raw, M.d_off, B, thr, limit, Lm, M.d_n, M.d_k, M.d_s, M.stream) != 0)
             return fail(kErrInternal);
         if (sim && queue_similarity(sim_view(*S, libs), M.d_raw, M.d_off, B, Lm, M.d_n, M.d_k, M.d_s, d_v, d_t, sim->metric, true,
                                         sim->min_sim, M.stream, M.d_raw) != 0)
@@ -4114,6 +4295,60 @@ NGS_API int ngsSetLocate(uint32_t set, uint32_t keyId, uint32_t* handle, uint32_
     return 0;
 }
 
+NGS_API int ngsDropDeadDevice(uint32_t* dCounts, uint32_t* dKeys, float* dScores, uint32_t n, uint32_t stride,
+                              const uint32_t* dDead, uint32_t nKeys, uint32_t limit, uint32_t* dShort, void* stream) {
+    if (!dCounts || (n && stride && (!dKeys || !dScores)) || (nKeys && !dDead) || n > kInt32Max) return -3;
+    DropBlocks D{};
+    D.b[0] = DropBlock{dCounts, dKeys, dScores, dDead, dShort, stride, nKeys};
+    return HIP_CHECK(launch_drop_dead(D, 1, n, limit, (hipStream_t)stream)) ? 0 : -4;
+}
+
+NGS_API int ngsSetRemove(uint32_t set, const uint32_t* keyIds, uint32_t n) { return set_mark(set, keyIds, n, true); }
+NGS_API int ngsSetRestore(uint32_t set, const uint32_t* keyIds, uint32_t n) { return set_mark(set, keyIds, n, false); }
+
+NGS_API uint32_t ngsSetLiveKeys(uint32_t set) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    return entry_set(set, S, libs) ? 0u : (uint32_t)(S->n_keys - S->n_dead);
+}
+
+NGS_API uint32_t ngsSetDeadKeys(uint32_t set, uint32_t* out, uint32_t cap) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (entry_set(set, S, libs) != 0) return 0;
+    uint32_t at = 0;
+    for (const KeySet::Member& m : S->parts)
+        for (size_t w = 0; out && at < cap && w < m.dead.size(); ++w)
+            for (uint32_t bits = m.dead[w]; bits && at < cap; bits &= bits - 1u)
+                out[at++] = m.base + (uint32_t)w * 32u + (uint32_t)__builtin_ctz(bits);
+    return (uint32_t)S->n_dead;
+}
+
+NGS_API int ngsSetIsLive(uint32_t set, uint32_t keyId) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (keyId >= S->n_keys) return -3;
+    size_t p = S->parts.size() - 1;
+    while (S->parts[p].base > keyId) --p;
+    const KeySet::Member& m = S->parts[p];
+    return m.dead.empty() || !dead_bit(m.dead.data(), m.n_keys, keyId - m.base) ? 1 : 0;
+}
+
+NGS_API int ngsSetDeadStats(uint32_t set, uint64_t* out, int n) {
+    std::shared_lock<std::shared_mutex> lk(g_lock);
+    KeySet* S = nullptr;
+    Library* libs[kSetMaxParts] = {};
+    if (const int rc = entry_set(set, S, libs)) return rc;
+    if (n < 0 || (n && !out)) return -3;
+    const uint64_t v[NGS_SET_DEAD_STATS] = {S->drop_launches.load(), S->re_searches.load(), S->max_fetch.load()};
+    for (int i = 0; i < n && i < (int)NGS_SET_DEAD_STATS; ++i) out[i] = v[i];
+    return (int)NGS_SET_DEAD_STATS;
+}
+
 NGS_API int ngsSetSearchDevice(uint32_t set, const uint8_t* dQueryBytes, const uint64_t* dQueryOffsets,
                                uint32_t nQueries, float threshold, uint32_t limit, uint32_t outStride,
                                uint32_t* dCounts, uint32_t* dKeys, float* dScores, void* stream) {
@@ -4136,7 +4371,7 @@ NGS_API int ngsSetSearchDevice(uint32_t set, const uint8_t* dQueryBytes, const u
     SetBlocks K;
     if (!set_blocks(M, *S, libs, nQueries, limit, K)) return -4;
     SetGuards guards(*S, libs);  // (until the final synchronise)
-    if (const int rc = set_search(*S, libs, K, dQueryBytes, dQueryOffsets, nQueries, threshold, limit, outStride, dCounts,
+    if (const int rc = set_search(*S, libs, M, K, dQueryBytes, dQueryOffsets, nQueries, threshold, limit, outStride, dCounts,
                                   dKeys, dScores, s))
         return rc;
     return HIP_CHECK(hipStreamSynchronize(s)) ? 0 : -4;
@@ -4227,7 +4462,7 @@ NGS_API int ngsSetSelfJoinDevice(uint32_t set, uint32_t firstKey, uint32_t nKeys
     if (!M.alloc(&M.d_raw, set_query_bytes(*S, libs, firstKey, nKeys) + 16) || !M.alloc(&M.d_off, (size_t)nKeys + 1) ||
         !set_blocks(M, *S, libs, nKeys, Ls, K))
         return -4;
-    return set_join_batch(*S, libs, K, firstKey, nKeys, threshold, limit, outStride, M.d_raw, M.d_off, dCounts, dKeys,
+    return set_join_batch(*S, libs, M, K, firstKey, nKeys, threshold, limit, outStride, M.d_raw, M.d_off, dCounts, dKeys,
                           dScores, (hipStream_t)stream, true);
 }
 
@@ -4287,7 +4522,9 @@ NGS_API uint32_t dedupKeysSet(uint32_t set, float threshold, uint32_t limit, uin
     if (S->n_keys == 0 || !HIP_CHECK(hipSetDevice(S->device))) return 0;
     SetGuards guards(*S, libs);
     SetJoin j{*S, libs};
-    return dedup_run(j, threshold, limit, metric, minSimilarity, batchKeys, labels);
+    // a dead key is alone under its own label (§9.9): the clusters of the live keys are counted
+    const uint32_t clusters = dedup_run(j, threshold, limit, metric, minSimilarity, batchKeys, labels);
+    return clusters > S->n_dead ? clusters - (uint32_t)S->n_dead : 0u;
 }
 
 NGS_API int ngsServeState(uint32_t handle) {

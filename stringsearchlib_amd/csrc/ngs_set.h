@@ -166,7 +166,101 @@ inline bool sim_set_record(const SimMember* m, uint32_t P, uint32_t g, uint32_t&
     return true;
 }
 
+// ---- dead keys: delete without a rebuild ----
+// Definition. A set keeps, per member, a dead mask of one bit per local key id (bit k & 31 of word
+// k >> 5). Every answer of a set with dead keys is the answer of a set over the same members with the
+// rows of the dead master keys left out, compared by key string, order and fp32 score bits; the
+// global key ids are the unchanged ones of the full set (base_p + k), so ids are stable under delete
+// as they are under append. The members themselves are never changed.
+//
+// Why it is exact: a key's score depends on its own row only, and the whole library's order is
+// (score desc, length asc, part asc, local id asc). Removing records from a totally ordered list
+// keeps the order of the rest.
+//
+// Row rule (drop_dead_row, k_drop_dead). Row i of a block in ngsSearchDevice's layout, in place: with
+// c = min(counts[i], stride), every record whose key k < n_keys has its dead bit set is removed (a
+// k >= n_keys is live, nothing is read through it); the remaining records keep their order and move
+// up; the row is cut to L = limit ? limit : 2^31-1; counts[i] is the new count. Cells past the new
+// count are unspecified, nothing at or beyond i * stride + stride is written. A row is short when
+// c == stride and fewer than L records are left: the search may have had more hits behind the block.
+//
+// The over-fetch (set_search). A member with d dead keys is searched at limit L + E into a block of
+// stride min(L + E, n_keys), then cut to L by the rule above. With E = d that is exact: the top L + d
+// of all keys hold the top L of the live ones. E starts at dead_first_fetch: what fills the search's
+// one-wave tier, kSetDeadFastLimit - L, while that is at least kSetDeadFetchMin (a search at a limit
+// above kSetDeadFastLimit leaves that tier for every query; §9.9 has what the two choices measured),
+// else max(L, kSetDeadFetch0); never more than d. A
+// member with a short row whose stride was below both L + d and n_keys is searched again with E grown
+// by kSetDeadFetchGrowth, capped at d (dead_next_fetch), until none is left.
+constexpr uint32_t kSetDeadFetch0 = 64;
+constexpr uint32_t kSetDeadFetchGrowth = 4;
+constexpr uint32_t kSetDeadFastLimit = 128;  // kWaveMaxLimit (ngs_common.h; ngs_abi.cpp asserts it)
+constexpr uint32_t kSetDeadFetchMin = 16;
+
+NGS_HD inline bool dead_bit(const uint32_t* dead, uint32_t n_keys, uint32_t k) {
+    return k < n_keys && ((dead[k >> 5] >> (k & 31u)) & 1u) != 0u;
+}
+// the first over-fetch of a member with d dead keys at limit L (= set_limit(limit))
+inline uint32_t dead_first_fetch(uint32_t d, uint32_t L) {
+    const bool fast = L <= kSetDeadFastLimit - kSetDeadFetchMin;
+    return std::min(d, fast ? kSetDeadFastLimit - L : std::max(L, kSetDeadFetch0));
+}
+// the one after E (0 < E < d)
+inline uint32_t dead_next_fetch(uint32_t d, uint32_t E) {
+    return (uint32_t)std::min<uint64_t>(d, (uint64_t)E * kSetDeadFetchGrowth);
+}
+// the stride of a member of n_keys keys searched at L + E: min(L + E, n_keys), the sum in 64 bits
+// (at or above 2^31-1 it means "all")
+inline uint32_t dead_fetch_stride(uint32_t L, uint32_t E, uint32_t n_keys) {
+    return (uint32_t)std::min<uint64_t>(std::min<uint64_t>((uint64_t)L + E, kSetLimitAll), n_keys);
+}
+
+// One block as k_drop_dead takes it, by value: 16 of them are the 768 bytes of DropBlocks.
+struct DropBlock {
+    uint32_t* counts;
+    uint32_t* keys;
+    float* scores;
+    const uint32_t* dead;
+    uint32_t* n_short;  // += the block's short rows (may be null)
+    uint32_t stride, n_keys;
+};
+static_assert(sizeof(DropBlock) == 48, "16 blocks x 48 bytes travel in the kernel arguments");
+struct DropBlocks {
+    DropBlock b[kSetMaxParts];
+};
+
+// ---- host reference routine (k_drop_dead restates it as a compaction by ballots) ----
+// The row rule on one row (keys / scores point at its first cell): returns the new count, and whether
+// the row is short in *is_short (may be null).
+inline uint32_t drop_dead_row(uint32_t count, uint32_t stride, uint32_t* keys, float* scores, const uint32_t* dead,
+                              uint32_t n_keys, uint32_t limit, bool* is_short) {
+    const uint32_t c = count < stride ? count : stride;
+    const uint32_t L = set_limit(limit);
+    uint32_t live = 0;
+    for (uint32_t r = 0; r < c; ++r) {
+        if (dead_bit(dead, n_keys, keys[r])) continue;
+        if (live < L && live != r) {
+            keys[live] = keys[r];
+            std::memcpy(scores + live, scores + r, sizeof(float));
+        }
+        ++live;
+    }
+    if (is_short) *is_short = c == stride && live < L;
+    return live < L ? live : L;
+}
+
 #if defined(__HIPCC__)
+// k_drop_dead over nb blocks of n rows each, in one launch (a grid over (row, block)); queued on s,
+// waits for nothing
+hipError_t launch_drop_dead(const DropBlocks& blocks, uint32_t nb, uint32_t n, uint32_t limit, hipStream_t s);
+// counts[i] = 0 for every row i < n whose global key id first + i is dead in its member (P members of
+// ascending bases, as SimMembers'; dead[p] may be null: no dead key there)
+struct DeadMasks {
+    const uint32_t* dead[kSetMaxParts];
+    uint32_t base[kSetMaxParts], n_keys[kSetMaxParts];
+};
+hipError_t launch_zero_dead_rows(const DeadMasks& masks, uint32_t P, uint32_t* counts, uint32_t n, uint32_t first,
+                                 hipStream_t s);
 // launch_similarity over the P members of T (character size cs, the first member's validChar set):
 // one launch for the whole block; terms (may be null) receives the members' local term ids.
 hipError_t launch_similarity_set(const SimMembers& T, uint32_t P, uint32_t cs, const uint32_t valid[8],

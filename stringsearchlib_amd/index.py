@@ -669,6 +669,16 @@ def merge_results_device(parts, n: int, limit: int, out_stride: int, d_counts: i
                                             stream or None), "ngsMergeResultsDevice")
 
 
+def drop_dead_device(d_counts: int, d_keys: int, d_scores: int, n: int, stride: int, d_dead: int, n_keys: int,
+                     limit: int = 0, d_short: int = 0, stream: int = 0) -> None:
+    """ngsDropDeadDevice on raw device pointers: the records of every row of the block whose key k < n_keys
+    has bit k & 31 of d_dead[k >> 5] set are removed in place, the rest keep their order and move up, the
+    row is cut to `limit`; *d_short (may be 0) is increased by the rows that filled the stride and were
+    left with fewer than `limit` records. Queued on `stream`; nothing waits."""
+    _ok(_native.lib().ngsDropDeadDevice(d_counts, d_keys or None, d_scores or None, n, stride, d_dead or None, n_keys,
+                                        limit, d_short or None, stream or None), "ngsDropDeadDevice")
+
+
 class IndexSet:
     """Indexes of one class and gram size searched as one library (ngsSet*): partitions of a library, or a
     base and the parts appended to it. Global key id = the keys of the earlier parts + the local id; the
@@ -721,6 +731,51 @@ class IndexSet:
     def key(self, key_id: int):
         index, k = self.locate(key_id)
         return index.key(k)
+
+    # -- dead keys: delete without a rebuild; to update a key, remove it and append the new row --
+    def _mark(self, what: str, key_ids) -> int:
+        ids = [int(g) for g in key_ids]
+        arr = (C.c_uint32 * max(1, len(ids)))(*ids)
+        rc = getattr(_native.lib(), what)(self.set_id, arr, len(ids))
+        if rc == -3:
+            raise IndexError(f"{what}: a key id at or past num_keys() (nothing was changed)")
+        _ok(min(rc, 0), what)
+        return rc
+
+    def remove(self, key_ids) -> int:
+        """ngsSetRemove: the global key ids become dead and leave every later answer of the set, which is
+        then that of a set without those keys' rows; ids, strings and the members stay as they are.
+        Returns the number of keys newly dead; IndexError, with nothing changed, for an id past the set."""
+        return self._mark("ngsSetRemove", key_ids)
+
+    def restore(self, key_ids) -> int:
+        """ngsSetRestore: the global key ids become live again; returns the number newly live."""
+        return self._mark("ngsSetRestore", key_ids)
+
+    def live_keys(self) -> int:
+        return _native.lib().ngsSetLiveKeys(self.set_id)
+
+    def dead_keys(self):
+        """The dead global key ids, ascending: what a caller stores to persist the set's deletions."""
+        L = _native.lib()
+        n = L.ngsSetDeadKeys(self.set_id, None, 0)
+        out = (C.c_uint32 * max(1, n))()
+        n = min(n, L.ngsSetDeadKeys(self.set_id, out, n))
+        return list(out[:n])
+
+    def is_live(self, key_id: int) -> bool:
+        rc = _native.lib().ngsSetIsLive(self.set_id, key_id)
+        if rc == -3:
+            raise IndexError(key_id)
+        _ok(min(rc, 0), "ngsSetIsLive")
+        return bool(rc)
+
+    def dead_stats(self) -> dict:
+        """ngsSetDeadStats: counters since the set was made."""
+        out = (C.c_uint64 * 3)()
+        rc = _native.lib().ngsSetDeadStats(self.set_id, out, 3)
+        _ok(min(rc, 0), "ngsSetDeadStats")
+        return {"drop_launches": out[0], "re_searches": out[1], "max_over_fetch": out[2]}
 
     def score_batch(self, queries, threshold: float = 0.0, limit: int = 100):
         """scoreBatchSet / W / U8 by the members' class: one list of (key, score) per query."""
@@ -838,7 +893,8 @@ class IndexSet:
         if not clusters:
             _check("dedupKeysSet")
         out = list(labels[:nk])
-        assert clusters == sum(1 for k, v in enumerate(out) if k == v)
+        # (a dead key is alone under its own label and is not counted)
+        assert clusters == sum(1 for k, v in enumerate(out) if k == v) - (nk - self.live_keys())
         return out
 
     def similarity_device(self, d_bytes: int, d_offsets: int, n: int, stride: int, d_counts: int, d_keys: int,
